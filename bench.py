@@ -1,10 +1,24 @@
 #!/usr/bin/env python3
-"""bench.py -- Msamples/s of the MI355X `path` integrator on BASELINE config C2,
-and on C3 (matpreview, BASELINE's second north-star scene), C4 (the 200k-triangle
-atrium BASELINE names for tile sharding), C5 (roughplastic with the
-rough-transmittance lookup) and C2g (C2 with the reference's default gaussian
-reconstruction filter) in the same run, as the line's `secondary` blocks (one
-per config, each with its own value, ms_per_step, roofline and CPU baseline).
+"""bench.py -- Msamples/s of the MI355X `path` integrator on BASELINE config C2.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline figure needs: it builds and uploads the scene, renders W untimed and K
+timed frames, writes the last frame if `--dump-outputs DIR` is given and prints
+the result line.  With `--full` the same run also measures, after the timed
+steps, the config's roofline (a bounded traversal-stats pass joined with the
+committed rocprofv3 profiles) and a same-run CPU baseline, and times C3
+(matpreview, BASELINE's second north-star scene), C4 (the 200k-triangle atrium
+BASELINE names for tile sharding), C5 (roughplastic with the rough-transmittance
+lookup) and C2g (C2 with the reference's default gaussian reconstruction filter)
+as the line's `secondary` blocks (one per config, each with its own value,
+ms_per_step, roofline and CPU baseline).  `--secondary`, `--no-cpu-baseline` and
+`--cpu-threads` narrow a `--full` run and do nothing without it.
+
+`--dump-outputs DIR`: rank 0 writes what the last timed step of `--config`
+computed, the reduced film a caller of the render path receives, as
+`DIR/film.npy` (float32, (H+2b) x (W+2b) x 5 with the filter border b; 18.5 MB for
+C2).  Scene, sampler and tile order are fixed by the arguments alone, so two
+builds run with the same arguments can be compared value for value.
 
 Workload (BASELINE.json configs[1]): Cornell box, 1280x720, 512 spp, sobol,
 path maxDepth=-1 rrDepth=5, box filter.  One step = one full frame
@@ -16,7 +30,7 @@ split evenly over 1-8 ranks) and the films are summed onto rank 0 with one RCCL 
 reference's Film::put merge, renderproc.cpp:142-149).  Total work is fixed as
 N grows: scaling "strong".
 
-Launch: `python bench.py [--gpus N --steps K --warmup W]`.  With N > 1 and no
+Launch: `python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]`.  With N > 1 and no
 torch.distributed environment, this process starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child
 (one process per GPU, RCCL backend) before touching the GPU, and exits with
@@ -38,6 +52,7 @@ import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs writes at most this much
 BASELINE_METRIC = 'Msamples/s (and s/frame) at 512 spp, 1280×720; 1/2/4/8 MI355X + CPU ref'
 WORKLOADS = {
     'C1': 'C1: Cornell box 512x512 64 spp (plumbing config)',
@@ -70,12 +85,22 @@ def parse_args(argv=None):
                     help='create the nccl (RCCL) process group and reduce the film over it even at --gpus 1 '
                          '(launched through torch.distributed.run --nproc-per-node 1): executes the RCCL merge '
                          'path on a one-GPU box')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='rank 0 writes the reduced film of the last timed step of --config as DIR/film.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the roofline (traversal-stats pass + committed '
+                         'profiles), the CPU baseline and the --secondary workloads; off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-threads', type=int, default=0)
     ap.add_argument('--secondary', default='C3,C4,C5,C2g',
-                    help="further workloads timed in the same run (comma-separated), each emitted as a block of "
-                         "the line's `secondary` object; 'none' to skip")
-    return ap.parse_args(argv)
+                    help="with --full: further workloads timed in the same run (comma-separated), each emitted as "
+                         "a block of the line's `secondary` object; 'none' to skip")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.warmup < 0:
+        ap.error('--warmup must be >= 0')
+    return args
 
 
 def _free_port():
@@ -444,10 +469,22 @@ def run_workload(config, args, world, rank, local, dist, torch, lib_hash):
     if args.save_film and config == args.config:
         import numpy as np
         np.save(args.save_film, film.cpu().numpy().reshape(H + 2 * b, W + 2 * b, 5))
+    if args.dump_outputs and config == args.config:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        out = film.cpu().numpy().astype(np.float32, copy=False).reshape(H + 2 * b, W + 2 * b, 5)
+        if out.nbytes > DUMP_MAX_BYTES:
+            # a frame past the dump budget (--size overrides only): a fixed, seeded sample of
+            # its pixels, 20 B of film + 8 B of index each, in ascending pixel order
+            px = out.reshape(-1, 5)
+            idx = np.sort(np.random.default_rng(0x5EED).choice(px.shape[0], DUMP_MAX_BYTES // 28, replace=False))
+            np.save(os.path.join(args.dump_outputs, 'film_pixels.npy'), idx.astype(np.float64))
+            out = px[idx]
+        np.save(os.path.join(args.dump_outputs, 'film.npy'), out)
     value = total_samples / elapsed_max / 1e6
     roofline = None
     cpu = None
-    if gpu:
+    if gpu and args.full:
         # roofline: traversal counters from a bounded stats pass (1/16 of the rows), always
         # through the BVH: tiny scenes' linear TriAccel scan (an implementation choice that
         # reads every record from the scalar cache) must not inflate the workload's bytes
@@ -498,7 +535,8 @@ def main():
             dist.init_process_group('gloo')   # RCCL refuses two ranks on one device
         elif world > 1 or args.rccl:
             dist.init_process_group('nccl', device_id=torch.device('cuda', dev))
-        lib_hash = lib_sha256()
+        if args.full:
+            lib_hash = lib_sha256()   # the roofline's profiles are stamped with the build they describe
     elif world > 1:
         dist.init_process_group('gloo')
     if world > 1:
@@ -506,7 +544,7 @@ def main():
 
     main_res = run_workload(args.config, args, world, rank, local, dist, torch, lib_hash)
     second = {}
-    if args.secondary and args.secondary.lower() != 'none' and not args.size:
+    if args.full and args.secondary and args.secondary.lower() != 'none' and not args.size:
         for cfg in [c.strip() for c in args.secondary.split(',') if c.strip()]:
             if cfg != args.config and cfg not in second:
                 second[cfg] = run_workload(cfg, args, world, rank, local, dist, torch, lib_hash)
@@ -520,7 +558,7 @@ def main():
             'unit': 'Msamples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': m['ms_per_step'], 'higher_is_better': True,
             'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': m['config'],
+            'full': bool(args.full), 'config': m['config'],
             'roofline': m['roofline'],
             'cpu_baseline': m['cpu_baseline'],
         }

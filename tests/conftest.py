@@ -12,6 +12,40 @@ from pkgimport import mitsuba_amd  # noqa: E402
 mitsuba_amd()
 
 
+GOLDEN = os.path.join(REPO, 'tests', 'golden')
+_unpacked = {}
+
+
+def golden_unpacked(sub, names):
+    """A temporary directory holding tests/golden/<sub>/<name>.xz, for each name,
+    decompressed (once per session; removed at exit).  These are the reference's
+    own data files, cut by tests/golden/make_reference_fixtures.py and stored
+    whole, so that no test reads anything outside the repository."""
+    import atexit
+    import lzma
+    import shutil
+    import tempfile
+    key = (sub, tuple(names))
+    if key not in _unpacked:
+        d = tempfile.mkdtemp(prefix='mtsgpu_golden_')
+        atexit.register(shutil.rmtree, d, ignore_errors=True)
+        for n in names:
+            with lzma.open(os.path.join(GOLDEN, sub, n + '.xz')) as f, open(os.path.join(d, n), 'wb') as out:
+                out.write(f.read())
+        _unpacked[key] = d
+    return _unpacked[key]
+
+
+def reference_microfacet_dir():
+    """The reference's data/microfacet (beckmann.dat, ggx.dat, phong.dat)."""
+    return golden_unpacked('microfacet', ('beckmann.dat', 'ggx.dat', 'phong.dat'))
+
+
+def reference_bunny_path():
+    """The reference's data/tests/bunny.ply."""
+    return os.path.join(golden_unpacked('', ('bunny.ply',)), 'bunny.ply')
+
+
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs an MI355X (gfx950) GPU')
 

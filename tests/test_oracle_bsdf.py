@@ -4,18 +4,17 @@ eval()/pdf() (relative/absolute error 1e-2 in single precision, :33-37), and a
 chi-square goodness-of-fit of sampled directions against the integrated pdf
 (significance 0.25% per test, :27-31)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 from scipy import stats
 
+from conftest import reference_microfacet_dir
 from mitsuba_amd.scene import BSDF, Checkerboard
 
 # roughplastic reads data/microfacet/<distribution>.dat: the reference's own
-# files when this container has them, else the in-tree generated tables
-REF_MICROFACET = '/root/reference/data/microfacet'
-RT_DIR = REF_MICROFACET if os.path.isdir(REF_MICROFACET) else None
+# files (tests/golden/microfacet, unpacked by conftest)
+RT_DIR = reference_microfacet_dir()
 
 ERROR_REQ = 1e-2
 CASES = {

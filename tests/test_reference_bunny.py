@@ -1,18 +1,14 @@
-"""The PLY loader on the reference's own data/tests/bunny.ply, read in place
-(it stays in /root/reference: copying it into the repository was refused,
-DESIGN.md 2), and C3 (matpreview) with the bunny as its object rendered by the
-CPU oracle.  Skipped where the reference is absent (the GPU boxes), so the GPU
-C3 keeps the procedural stand-in (scenes.blob_mesh)."""
-import os
-
+"""The PLY loader on the reference's own data/tests/bunny.ply (stored whole,
+xz-compressed, as tests/golden/bunny.ply.xz; conftest.reference_bunny_path unpacks
+it), and C3 (matpreview) with the bunny as its object rendered by the CPU
+oracle.  The benchmark's C3 keeps the procedural stand-in (scenes.blob_mesh)."""
 import numpy as np
-import pytest
 
+from conftest import reference_bunny_path
 from mitsuba_amd import ply, scenes
 from mitsuba_amd.transform import Transform
 
-BUNNY = '/root/reference/data/tests/bunny.ply'
-pytestmark = pytest.mark.skipif(not os.path.isfile(BUNNY), reason='reference data not in this container')
+BUNNY = reference_bunny_path()
 
 
 def _bunny_world():

@@ -5,21 +5,22 @@ configure() errors (mtsgpu_check_scene) next to the oracle's.
 
 Pinning: the generator (tools/rtrans_nd.c, the reference's rdielprec.cpp +
 NDIntegrator restated) is checked against the reference's own
-data/microfacet/*.dat when this container has them (the files stay in
-/root/reference; nothing is copied), and a reduced C5 is rendered by the
-oracle on both tables: that image difference is C5's stated tolerance
-(DESIGN.md 2)."""
+data/microfacet/*.dat (stored whole, xz-compressed, under
+tests/golden/microfacet; conftest.reference_microfacet_dir unpacks them), and
+a reduced C5 is rendered by the oracle on both tables: that image difference
+is C5's stated tolerance."""
 import os
 import struct
 
 import numpy as np
 import pytest
 
+from conftest import reference_microfacet_dir
 from mitsuba_amd import rtrans, scenes, xmlscene
 from mitsuba_amd.integrator import MtsgpuError, check_scene
 from mitsuba_amd.scene import BSDF, Checkerboard
 
-REF = '/root/reference/data/microfacet'
+REF = reference_microfacet_dir()
 
 
 def _load(path):
@@ -45,7 +46,6 @@ def test_generated_tables_layout(name, alphas, amax):
 
 
 # measured: bit-identical entries, |diff| <= 1e-6, p99, max
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference data not in this container')
 @pytest.mark.parametrize('name,exact,close,p99,dmax', [('beckmann', 0.65, 0.987, 3e-5, 3e-3),
                                                        ('ggx', 0.60, 0.986, 5e-5, 2e-2),
                                                        ('phong', 0.54, 0.957, 2e-5, 1e-2)])
@@ -58,7 +58,6 @@ def test_generated_tables_match_reference(name, exact, close, p99, dmax):
     assert stats[0] > exact and stats[1] > close and stats[2] < p99 and stats[3] < dmax, stats
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference data not in this container')
 def test_c5_image_on_reference_vs_generated_tables(oracle):
     """C5's tolerance: the same reduced C5 frame, rendered by the oracle on the
     reference's ggx.dat and on the generated one."""
@@ -78,13 +77,11 @@ def test_c5_image_on_reference_vs_generated_tables(oracle):
     assert rel_rmse < 2e-5, rel_rmse          # measured 9.8e-6
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference data not in this container')
 def test_c5_configuration_row_band_reference_vs_generated_tables(oracle):
     """C5's tolerance at C5's own configuration: the full
     1280-wide frame geometry, the 1024x512 envmap, the full blob mesh and 1024
     spp, over a band of full-width rows through the roughplastic object,
-    rendered by the oracle on the reference's data/microfacet/ggx.dat (read in
-    place) and on the generated table (what the GPU box uses).  Bounds: the
+    rendered by the oracle on the reference's data/microfacet/ggx.dat and on the generated table (what the GPU box uses).  Bounds: the
     band's rel-RMSE and the per-pixel relative error of every pixel with
     non-negligible radiance (DESIGN.md 2 records the measured values)."""
     films = []
@@ -139,7 +136,6 @@ def test_c5_layer_fixture_carries_reference_values(c5_reference_tables):
     rtrans._cache.clear()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference data not in this container')
 def test_c5_layer_fixture_equals_reference_file(oracle, c5_reference_tables):
     """The fixture against the file it was cut from (make_rtrans_layers.py), and the
     proof that the layers it keeps are all C5 reads: the oracle renders a reduced

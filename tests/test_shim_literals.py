@@ -11,43 +11,30 @@ this test checks every such literal against what the reference registers:
 - plugin names (``getPluginName()``, the CPU integrator behind ``Li``) must be
   plugins the reference builds (``src/**/<name>.cpp``).
 
-Needs ``/root/reference`` (the CPU container); skipped elsewhere.
+The reference's registry and plugin names are the lists in
+``tests/golden/reference_names.json`` (names only, cut from the reference's
+sources by ``tests/golden/make_reference_fixtures.py``).
 """
+import json
 import os
 import re
 
-import pytest
-
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
+NAMES = os.path.join(REPO, 'tests', 'golden', 'reference_names.json')
 SHIM = os.path.join(REPO, 'integration', 'gpupath.cpp')
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'src')),
-                                reason='reference sources not present')
 
 
 def _registry():
-    """{class name: abstract?} from every MTS_IMPLEMENT_CLASS[_S] in the reference."""
-    reg = {}
-    pat = re.compile(r'MTS_IMPLEMENT_CLASS(?:_S)?\(\s*(\w+)\s*,\s*(true|false)\s*,')
-    for root in ('src', 'include'):
-        for dp, _, fns in os.walk(os.path.join(REF, root)):
-            for fn in fns:
-                if not fn.endswith(('.cpp', '.h', '.inl')):
-                    continue
-                with open(os.path.join(dp, fn), errors='replace') as f:
-                    for m in pat.finditer(f.read()):
-                        reg[m.group(1)] = reg.get(m.group(1), True) and m.group(2) == 'true'
-    return reg
+    """{class name: abstract?} of every MTS_IMPLEMENT_CLASS[_S] in the reference."""
+    with open(NAMES) as f:
+        names = json.load(f)
+    return dict([(n, True) for n in names['abstract']] + [(n, False) for n in names['concrete']])
 
 
 def _plugins():
-    names = set()
-    for dp, _, fns in os.walk(os.path.join(REF, 'src')):
-        for fn in fns:
-            if fn.endswith('.cpp'):
-                names.add(fn[:-4])
-    return names
+    """The plugins the reference builds (``src/**/<name>.cpp``)."""
+    with open(NAMES) as f:
+        return set(json.load(f)['plugins'])
 
 
 def _shim():
