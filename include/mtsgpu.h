@@ -410,6 +410,15 @@ int mtsgpu_kdtree_host(const mtsgpu_scene_desc *scene, uint32_t *nodes, size_t n
  * (src/librender/skdtree.cpp) as rebuilt here. */
 int mtsgpu_bvh_host(const mtsgpu_scene_desc *scene, uint32_t *nodes, size_t node_cap, uint32_t *hnodes,
                     size_t hnode_cap, uint32_t *qnodes, size_t qnode_cap, uint32_t *info4, char *msg, size_t cap);
+/* Host-only (no device needed): configure `scene` and export the tiny-scene
+ * scan's layout as upload_scene forms it: counts = the six group sizes (2k:
+ * projection axis k general, 2k+1: plane normal to axis k) followed by the six
+ * groups' pair counts; each group leads with its pairs (records sharing plane
+ * and vertex A, partners adjacent), its singles follow.  `records` (12 words
+ * each: k, n_u, n_v, n_d, a_u, a_v, b_nu, b_nv, c_nu, c_nv, prim, shape) is
+ * copied when `cap` (in words) suffices.  All counts are 0 for a scene the
+ * kernels do not scan (more than 64 triangles, or analytic shapes). */
+int mtsgpu_scan_host(const mtsgpu_scene_desc *scene, float *records, size_t cap, uint32_t counts[12]);
 /* Diagnostics (tests): device arithmetic probe -- for each i, out[8i..8i+7] =
  * {a/b, sqrt|a|, sin a, cos a, acos(clamp a), atan2(a,b), exp(-|a|), a*b+a}
  * computed by the kernels' own routines; scene info = {nodes, prims, depth, CUs}. */

@@ -88,7 +88,7 @@ struct mtsgpu_ctx {
     HostScene host;
     MtsgDeviceScene dscene;
     DevBuf scan_tris;   // k-grouped TriAccel records of scan-sized scenes
-    uint32_t scan_n[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t scan_n[6] = {0, 0, 0, 0, 0, 0};   // as MtsgLaunch::scan_n: records | plane pairs << 16
     DevBuf nodes, hnodes, tris, prim_vtx, dpdu, positions, normals, shapes, bsdfs, emitters, area_cdf, em_cdf, sobol;
     DevBuf env, env_texels, env_rows, env_cols, env_weights, env_grows, env_gcols;
     DevBuf rtrans, texcoords, analytic;
@@ -194,6 +194,53 @@ int mtsgpu_create(int device, mtsgpu_ctx **out) {
     return MTSGPU_OK;
 }
 
+// tiny scenes: the TriAccel records grouped by projection axis and, within
+// an axis, planes normal to it (n_u = n_v = 0: the Cornell box's walls)
+// last, so the scan runs six branch-free loops, the aligned ones without
+// the numerator's and denominator's n_u/n_v terms (the closest hit and its
+// tie rule do not depend on the order the records are tested in).
+// Within a group, records that share their plane and vertex A -- the two
+// triangles of a quad triangulated as a fan -- come first, partners adjacent
+// at 2i and 2i+1 (np[group] pairs), the singles after them: a pair's t, hu
+// and hv are the same bits for both, so scan_pair forms them once.  Partners
+// have a_u and a_v bit-equal and n_u, n_v, n_d bit-equal (an aligned group:
+// n_d only, its loops never read n_u / n_v).  Bit-equality is an equivalence,
+// so pairing each record with the next unpaired equal one leaves at most one
+// single per plane.  MTSGPU_NO_SCAN_PAIRS: no pairs (A/B and tests).
+static void mtsg_scan_layout(const std::vector<MtsgTri> &tris, std::vector<MtsgTri> &g, uint32_t n[6], uint32_t np[6]) {
+    const bool pairs = !std::getenv("MTSGPU_NO_SCAN_PAIRS");
+    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    g.clear();
+    for (uint32_t k = 0; k < 3; ++k)
+        for (uint32_t al = 0; al < 2; ++al) {
+            std::vector<MtsgTri> m, singles;
+            for (const MtsgTri &t : tris)
+                if (t.k == k && (uint32_t)(t.n_u == 0.0f && t.n_v == 0.0f) == al) m.push_back(t);
+            std::vector<char> used(m.size(), 0);
+            uint32_t &cnt = np[2 * k + al];
+            cnt = 0;
+            for (size_t i = 0; i < m.size(); ++i) {
+                if (used[i]) continue;
+                size_t j = m.size();
+                if (pairs)
+                    for (j = i + 1; j < m.size(); ++j)
+                        if (!used[j] && bits(m[i].a_u) == bits(m[j].a_u) && bits(m[i].a_v) == bits(m[j].a_v) &&
+                            bits(m[i].n_d) == bits(m[j].n_d) &&
+                            (al || (bits(m[i].n_u) == bits(m[j].n_u) && bits(m[i].n_v) == bits(m[j].n_v))))
+                            break;
+                if (j < m.size()) {
+                    used[j] = 1;
+                    g.push_back(m[i]);
+                    g.push_back(m[j]);
+                    cnt++;
+                } else
+                    singles.push_back(m[i]);
+            }
+            g.insert(g.end(), singles.begin(), singles.end());
+            n[2 * k + al] = (uint32_t)m.size();
+        }
+}
+
 int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     if (!ctx || !scene) return MTSGPU_EINVAL;
     ctx->have_scene = false;
@@ -213,18 +260,13 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
         (e = upload(ctx->emitters, H.emitters, s)) != hipSuccess || (e = upload(ctx->area_cdf, H.area_cdf, s)) != hipSuccess ||
         (e = upload(ctx->em_cdf, H.em_cdf, s)) != hipSuccess || (e = upload(ctx->sobol, sobol_nibble_tables(), s)) != hipSuccess)
         return hip_fail(ctx, e, "scene upload");
-    // tiny scenes: the TriAccel records grouped by projection axis and, within
-    // an axis, planes normal to it (n_u = n_v = 0: the Cornell box's walls)
-    // last, so the scan runs six branch-free loops, the aligned ones without
-    // the numerator's and denominator's n_u/n_v terms (the closest hit and its
-    // tie rule do not depend on the order the records are tested in)
+    // tiny scenes: the scan's grouped records (mtsg_scan_layout)
     for (uint32_t &c : ctx->scan_n) c = 0;
     if (H.tris.size() <= MTSG_SCAN_MAX && H.analytic.empty()) {
         std::vector<MtsgTri> g;
-        for (uint32_t k = 0; k < 3; ++k)
-            for (uint32_t al = 0; al < 2; ++al)
-                for (const MtsgTri &t : H.tris)
-                    if (t.k == k && (uint32_t)(t.n_u == 0.0f && t.n_v == 0.0f) == al) { g.push_back(t); ctx->scan_n[2 * k + al]++; }
+        uint32_t n[6], np[6];
+        mtsg_scan_layout(H.tris, g, n, np);
+        for (int k = 0; k < 6; ++k) ctx->scan_n[k] = n[k] | np[k] << 16;
         if (g.empty()) g.push_back(MtsgTri{});
         if ((e = upload(ctx->scan_tris, g, s)) != hipSuccess) return hip_fail(ctx, e, "scene upload");
     }
@@ -1125,6 +1167,20 @@ int mtsgpu_bvh_host(const mtsgpu_scene_desc *scene, uint32_t *nodes, size_t node
     if (nodes && node_cap >= H.nodes.size() * 16) std::memcpy(nodes, H.nodes.data(), H.nodes.size() * 64);
     if (hnodes && hnode_cap >= H.hnodes.size() * 8) std::memcpy(hnodes, H.hnodes.data(), H.hnodes.size() * 32);
     if (qnodes && qnode_cap >= H.qnodes.size() * 16) std::memcpy(qnodes, H.qnodes.data(), H.qnodes.size() * 64);
+    return MTSGPU_OK;
+}
+
+int mtsgpu_scan_host(const mtsgpu_scene_desc *scene, float *records, size_t cap, uint32_t counts[12]) {
+    if (!scene || !counts) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    const int rc = mtsg_configure_scene(scene, H, err);
+    if (rc) return rc;
+    for (int i = 0; i < 12; ++i) counts[i] = 0;
+    if (H.tris.size() > MTSG_SCAN_MAX || !H.analytic.empty()) return MTSGPU_OK;   // not a scan scene
+    std::vector<MtsgTri> g;
+    mtsg_scan_layout(H.tris, g, counts, counts + 6);
+    if (records && cap >= g.size() * 12) std::memcpy(records, g.data(), g.size() * sizeof(MtsgTri));
     return MTSGPU_OK;
 }
 

@@ -431,9 +431,10 @@ __device__ __forceinline__ bool scan_tris(const MtsgLaunch &L, f3 o, f3 d, float
     bestPrim = 0;
     bt = maxt;
 #define MTSG_SCAN_GROUP(K, AL)                                                                                   \
-    if (scan_k<K, AL, ANY, STATS>(tris, L.scan_n[2 * K + AL], o, d, mint, found, bestPrim, bu, bv, bt, tests)) \
+    if (scan_k<K, AL, ANY, STATS>(tris, L.scan_n[2 * K + AL] & 0xffffu, o, d, mint, found, bestPrim, bu, bv, bt, \
+                                  tests))                                                                        \
         return true;                                                                                             \
-    tris += L.scan_n[2 * K + AL];
+    tris += L.scan_n[2 * K + AL] & 0xffffu;
     MTSG_SCAN_GROUP(0, false) MTSG_SCAN_GROUP(0, true) MTSG_SCAN_GROUP(1, false) MTSG_SCAN_GROUP(1, true)
     MTSG_SCAN_GROUP(2, false) MTSG_SCAN_GROUP(2, true)
 #undef MTSG_SCAN_GROUP
@@ -464,10 +465,18 @@ __device__ __forceinline__ float div_by_rcp(float a, float b, float y) {
 
 // FAST (axis-aligned groups only): the two quotients through div_by_rcp with
 // the rays' reciprocals yS = RN(1/s_k), yC = RN(1/c_k)
+// The group's first np pairs of records (tris[2i], tris[2i + 1]) share their
+// plane and vertex A bit for bit (capi.cpp mtsg_scan_layout: the two triangles
+// of a quad), so num, both quotients and each ray's hu, hv are formed once for
+// the two; only the barycentrics and the acceptance run per partner.  Every
+// lane ends with what two successive single iterations give it: partner 1's
+// interval test would read tC against bt after partner 0, which is either
+// unchanged or tC itself, so it passes whenever partner 0's did and is not
+// repeated; on that tie the prim > bestPrim rule decides as before.
 template <int K, bool AL, bool FAST, bool STATS>
-__device__ __forceinline__ void scan_pair_k(cst_tri *tris, uint32_t n, f3 o, f3 ds, f3 dc, float minS, float maxS,
-                                            float minC, bool &occ, bool &found, uint32_t &bestPrim, float &bu,
-                                            float &bv, float &bt, unsigned long long &tests, float yS = 0,
+__device__ __forceinline__ void scan_pair_k(cst_tri *tris, uint32_t n, uint32_t np, f3 o, f3 ds, f3 dc, float minS,
+                                            float maxS, float minC, bool &occ, bool &found, uint32_t &bestPrim,
+                                            float &bu, float &bv, float &bt, unsigned long long &tests, float yS = 0,
                                             float yC = 0) {
     const float o_u = K == 0 ? o.y : K == 1 ? o.z : o.x, o_v = K == 0 ? o.z : K == 1 ? o.x : o.y,
                 o_k = K == 0 ? o.x : K == 1 ? o.y : o.z;
@@ -475,7 +484,46 @@ __device__ __forceinline__ void scan_pair_k(cst_tri *tris, uint32_t n, f3 o, f3 
                 s_k = K == 0 ? ds.x : K == 1 ? ds.y : ds.z;
     const float c_u = K == 0 ? dc.y : K == 1 ? dc.z : dc.x, c_v = K == 0 ? dc.z : K == 1 ? dc.x : dc.y,
                 c_k = K == 0 ? dc.x : K == 1 ? dc.y : dc.z;
-    for (uint32_t i = 0; i < n; ++i) {
+    for (uint32_t i = 0; i < np; ++i) {
+        if (STATS) tests += 4;
+        cst_tri &tr = tris[2 * i], &tq = tris[2 * i + 1];
+        const float n_u = tr.n_u, n_v = tr.n_v, n_d = tr.n_d, a_u = tr.a_u, a_v = tr.a_v;
+        const float b_nu0 = tr.b_nu, b_nv0 = tr.b_nv, c_nu0 = tr.c_nu, c_nv0 = tr.c_nv;
+        const float b_nu1 = tq.b_nu, b_nv1 = tq.b_nv, c_nu1 = tq.c_nu, c_nv1 = tq.c_nv;
+        const uint32_t prim0 = tr.prim, prim1 = tq.prim;
+        const float num = AL ? n_d - o_k : n_d - o_u * n_u - o_v * n_v - o_k;
+        const float tS = (AL && FAST) ? div_by_rcp(num, s_k, yS) : num / (AL ? s_k : s_u * n_u + s_v * n_v + s_k);
+        const float tC = (AL && FAST) ? div_by_rcp(num, c_k, yC) : num / (AL ? c_k : c_u * n_u + c_v * n_v + c_k);
+        if (!(tS < minS || tS > maxS)) {
+            const float hu = o_u + tS * s_u - a_u;
+            const float hv = o_v + tS * s_v - a_v;
+            const float u0 = hv * b_nu0 + hu * b_nv0;
+            const float v0 = hu * c_nu0 + hv * c_nv0;
+            if (u0 >= 0 && v0 >= 0 && u0 + v0 <= 1.0f) occ = true;
+            const float u1 = hv * b_nu1 + hu * b_nv1;
+            const float v1 = hu * c_nu1 + hv * c_nv1;
+            if (u1 >= 0 && v1 >= 0 && u1 + v1 <= 1.0f) occ = true;
+        }
+        if (!(tC < minC || tC > bt)) {
+            const float hu = o_u + tC * c_u - a_u;
+            const float hv = o_v + tC * c_v - a_v;
+            const float u0 = hv * b_nu0 + hu * b_nv0;
+            const float v0 = hu * c_nu0 + hv * c_nv0;
+            if (u0 >= 0 && v0 >= 0 && u0 + v0 <= 1.0f) {
+                if (!found || tC < bt || prim0 > bestPrim) {
+                    found = true; bestPrim = prim0; bt = tC; bu = u0; bv = v0;
+                }
+            }
+            const float u1 = hv * b_nu1 + hu * b_nv1;
+            const float v1 = hu * c_nu1 + hv * c_nv1;
+            if (u1 >= 0 && v1 >= 0 && u1 + v1 <= 1.0f) {
+                if (!found || tC < bt || prim1 > bestPrim) {
+                    found = true; bestPrim = prim1; bt = tC; bu = u1; bv = v1;
+                }
+            }
+        }
+    }
+    for (uint32_t i = 2 * np; i < n; ++i) {
         if (STATS) tests += 2;
         cst_tri &tr = tris[i];
         const float n_u = tr.n_u, n_v = tr.n_v, n_d = tr.n_d, a_u = tr.a_u, a_v = tr.a_v, b_nu = tr.b_nu,
@@ -518,21 +566,27 @@ __device__ __forceinline__ void scan_pair(const MtsgLaunch &L, f3 o, f3 ds, f3 d
     bt = maxC;
     // a disabled ray (empty interval) may take the fast quotient whatever its direction
     const bool offS = !(minS <= maxS), offC = !(minC <= maxC);
+    // scan_n: records | leading pairs << 16 per group (the rare slow aligned
+    // pass tests its pairs as singles: the same result, less code)
 #define MTSG_SCAN_GROUP(K)                                                                                         \
-    scan_pair_k<K, false, false, STATS>(tris, L.scan_n[2 * K], o, ds, dc, minS, maxS, minC, occ, found, bestPrim,   \
-                                        bu, bv, bt, tests);                                                        \
-    tris += L.scan_n[2 * K];                                                                                       \
-    if (L.scan_n[2 * K + 1]) {                                                                                     \
-        const float s_k = K == 0 ? ds.x : K == 1 ? ds.y : ds.z, c_k = K == 0 ? dc.x : K == 1 ? dc.y : dc.z;        \
-        const bool fast = (offS || (minS >= 0x1p-30f && fabsf(s_k) >= 0x1p-60f)) &&                                \
-                          (offC || (minC >= 0x1p-30f && fabsf(c_k) >= 0x1p-60f));                                  \
-        if (__all(fast))                                                                                           \
-            scan_pair_k<K, true, true, STATS>(tris, L.scan_n[2 * K + 1], o, ds, dc, minS, maxS, minC, occ, found,  \
-                                              bestPrim, bu, bv, bt, tests, 1.0f / s_k, 1.0f / c_k);                \
-        else                                                                                                       \
-            scan_pair_k<K, true, false, STATS>(tris, L.scan_n[2 * K + 1], o, ds, dc, minS, maxS, minC, occ, found, \
-                                               bestPrim, bu, bv, bt, tests);                                       \
-        tris += L.scan_n[2 * K + 1];                                                                               \
+    {                                                                                                              \
+        const uint32_t ng = L.scan_n[2 * K] & 0xffffu, na = L.scan_n[2 * K + 1] & 0xffffu;                         \
+        scan_pair_k<K, false, false, STATS>(tris, ng, L.scan_n[2 * K] >> 16, o, ds, dc, minS, maxS, minC, occ,     \
+                                            found, bestPrim, bu, bv, bt, tests);                                   \
+        tris += ng;                                                                                                \
+        if (na) {                                                                                                  \
+            const float s_k = K == 0 ? ds.x : K == 1 ? ds.y : ds.z, c_k = K == 0 ? dc.x : K == 1 ? dc.y : dc.z;    \
+            const bool fast = (offS || (minS >= 0x1p-30f && fabsf(s_k) >= 0x1p-60f)) &&                            \
+                              (offC || (minC >= 0x1p-30f && fabsf(c_k) >= 0x1p-60f));                              \
+            if (__all(fast))                                                                                       \
+                scan_pair_k<K, true, true, STATS>(tris, na, L.scan_n[2 * K + 1] >> 16, o, ds, dc, minS, maxS,      \
+                                                  minC, occ, found, bestPrim, bu, bv, bt, tests, 1.0f / s_k,       \
+                                                  1.0f / c_k);                                                     \
+            else                                                                                                   \
+                scan_pair_k<K, true, false, STATS>(tris, na, 0, o, ds, dc, minS, maxS, minC, occ, found,           \
+                                                   bestPrim, bu, bv, bt, tests);                                   \
+            tris += na;                                                                                            \
+        }                                                                                                          \
     }
     MTSG_SCAN_GROUP(0) MTSG_SCAN_GROUP(1) MTSG_SCAN_GROUP(2)
 #undef MTSG_SCAN_GROUP

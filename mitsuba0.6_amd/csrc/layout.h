@@ -308,6 +308,9 @@ struct MtsgLaunch {
     const MtsgTri *scan_tris;         // the scan's TriAccel records grouped by projection axis k = 0, 1, 2
     uint32_t scan_n[6];               // and within k by n_u = n_v = 0 (2k: general, 2k+1: axis-aligned plane);
                                       // degenerate k = 3 records dropped; counts per group
+                                      // in the low 16 bits; the high 16: each group leads with that many pairs
+                                      // of records sharing plane and vertex A (partners at 2i, 2i + 1), its
+                                      // singles follow (capi.cpp mtsg_scan_layout)
     uint32_t num_verts, num_shapes;   // sizes of the triangle data SCENE_LDS kernels stage in LDS
     int32_t integrator;               // MTSGPU_INTEGRATOR_*
     uint32_t sampler;                 // MTSGPU_SAMPLER_*

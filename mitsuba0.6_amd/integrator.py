@@ -32,7 +32,7 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_group_render', 'mtsgpu_group_render_device', 'mtsgpu_group_member', 'mtsgpu_group_last_error',
            'mtsgpu_group_destroy', 'mtsgpu_trace_rays_ex', 'mtsgpu_debug_kdtree', 'mtsgpu_kdtree_host', 'mtsgpu_debug_libm',
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
-           'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex']
+           'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host']
 
 _lib = None
 
@@ -86,6 +86,8 @@ def load_library(path=None):
                                      P(C.c_uint32), C.c_char_p, C.c_size_t]
     L.mtsgpu_bvh_host.argtypes = [P(abi.SceneDesc), P(C.c_uint32), C.c_size_t, P(C.c_uint32), C.c_size_t,
                                   P(C.c_uint32), C.c_size_t, P(C.c_uint32), C.c_char_p, C.c_size_t]
+    if hasattr(L, 'mtsgpu_scan_host'):   # added within ABI 8: an A/B library of an earlier build has none
+        L.mtsgpu_scan_host.argtypes = [P(abi.SceneDesc), P(C.c_float), C.c_size_t, P(C.c_uint32)]
     L.mtsgpu_group_create.argtypes = [P(C.c_int), C.c_int, P(C.c_void_p)]
     L.mtsgpu_group_size.argtypes = [C.c_void_p]
     L.mtsgpu_group_upload_scene.argtypes = [C.c_void_p, P(abi.SceneDesc)]
@@ -137,6 +139,23 @@ def bvh_host(scene):
     if rc != 0:
         raise MtsgpuError(rc, buf.value.decode())
     return n, h, q, int(info[3])
+
+
+def scan_host(scene):
+    """The tiny-scene scan's record layout, formed on the host without a device
+    (mtsgpu_scan_host): (records (N, 12) uint32 MtsgTri words, the six group sizes,
+    the six groups' pair counts).  N = 0 for a scene the kernels do not scan."""
+    L = load_library()
+    d = scene.desc()
+    counts = (C.c_uint32 * 12)()
+    rc = L.mtsgpu_scan_host(C.byref(d), None, 0, counts)
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_scan_host')
+    rec = np.zeros((sum(counts[:6]), 12), np.uint32)
+    rc = L.mtsgpu_scan_host(C.byref(d), rec.ctypes.data_as(C.POINTER(C.c_float)), rec.size, counts)
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_scan_host')
+    return rec, list(counts[:6]), list(counts[6:])
 
 
 def kdtree_host(scene):

@@ -1,0 +1,145 @@
+"""The tiny-scene scan's record layout as upload_scene forms it, seen through
+mtsgpu_scan_host (no device): records grouped by projection axis and aligned
+flag, each group led by its plane pairs -- records that share plane and vertex
+A bit for bit, partners adjacent -- with the singles after them
+(capi.cpp mtsg_scan_layout, dpath.h scan_pair_k)."""
+import numpy as np
+import pytest
+
+from mitsuba_amd import scenes
+from mitsuba_amd.integrator import scan_host
+from mitsuba_amd.scene import BSDF, Mesh
+
+# MtsgTri words (csrc/layout.h)
+K, N_U, N_V, N_D, A_U, A_V, B_NU, B_NV, C_NU, C_NV, PRIM, SHAPE = range(12)
+
+
+def _with_meshes(extra, keep=None):
+    """C1's sensor, BSDFs and light with `extra` meshes in place of (keep=()) or
+    added to (keep=None) the room and its blocks."""
+    sc, _ = scenes.build('C1', width=8, height=8, spp=1)
+    room = sc.meshes[:-1] if keep is None else [sc.meshes[i] for i in keep]
+    sc.meshes = room + list(extra) + [sc.meshes[-1]]
+    return sc
+
+
+def _tri_mesh(pts, idx):
+    return Mesh(np.asarray(pts, np.float32), np.asarray(idx, np.uint32), bsdf=0, faceNormals=True)
+
+
+def tie_scene():
+    """The duplicated-block scene of tests/test_gpu_scan.py: every face of the
+    short block twice, and a degenerate triangle."""
+    sc, _ = scenes.build('C1', width=8, height=8, spp=1)
+    short = sc.meshes[5]
+    sc.bsdfs = list(sc.bsdfs) + [BSDF('diffuse', reflectance=(0.1, 0.3, 0.9))]
+    dup = Mesh(short.positions.copy(), short.indices.copy(), bsdf=len(sc.bsdfs) - 1, faceNormals=True)
+    degen = _tri_mesh([[0.5, 0.5, 0.5], [1.0, 1.0, 1.0], [1.5, 1.5, 1.5]], [[0, 1, 2]])
+    sc.meshes = list(sc.meshes) + [dup, degen]
+    return sc
+
+
+# a pentagon in the plane x + z = 4 (dyadic coordinates: every TriAccel field of
+# its fan is exact, so the three records' plane fields are the same bits)
+PENTAGON = [[1.0, 1.0, 3.0], [2.0, 1.0, 2.0], [2.5, 2.0, 1.5], [1.5, 3.0, 2.5], [0.5, 2.0, 3.5]]
+LONE = [[3.0, 0.5, 1.0], [4.0, 0.75, 1.5], [3.5, 2.0, 2.25]]
+
+
+def pentagon_scene():
+    return _with_meshes([_tri_mesh(PENTAGON, [[0, 1, 2], [0, 2, 3], [0, 3, 4]]), _tri_mesh(LONE, [[0, 1, 2]])], keep=())
+
+
+def one_triangle_scene():
+    sc, _ = scenes.build('C1', width=8, height=8, spp=1)
+    light = sc.meshes[-1]
+    sc.meshes = [Mesh(light.positions[:3].copy(), np.array([[0, 1, 2]], np.uint32), bsdf=-1, emitter=0,
+                      faceNormals=True)]
+    return sc
+
+
+def full_scene():
+    """MTSG_SCAN_MAX = 64 triangles: 19 fan quads on tilted planes, 24 lone
+    triangles and the light's two."""
+    rng = np.random.RandomState(7)
+    meshes = []
+    for _ in range(19):
+        o = rng.randint(4, 40, 3) / 8.0
+        e1, e2 = rng.randint(-8, 9, 3) / 8.0, rng.randint(-8, 9, 3) / 8.0
+        if not np.any(np.cross(e1, e2)):
+            e1, e2 = np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.5, 0.0])
+        meshes.append(_tri_mesh([o, o + e1, o + e1 + e2, o + e2], [[0, 1, 2], [0, 2, 3]]))
+    for _ in range(24):
+        meshes.append(_tri_mesh(rng.uniform(0.5, 5.0, (3, 3)), [[0, 1, 2]]))
+    sc = _with_meshes(meshes, keep=())
+    assert sc.num_triangles == 64
+    return sc
+
+
+SCENES = {'C2': lambda: scenes.build('C2')[0], 'ties': tie_scene, 'pentagon': pentagon_scene,
+          'one': one_triangle_scene, 'full': full_scene}
+
+
+def _groups(rec, n):
+    off = np.concatenate([[0], np.cumsum(n)])
+    return [rec[off[g]:off[g + 1]] for g in range(6)]
+
+
+def _aligned(r):
+    f = r.view(np.float32)
+    return bool(f[N_U] == 0.0 and f[N_V] == 0.0)
+
+
+def _key(r, al):
+    """what partners must share, bit for bit"""
+    return tuple(int(r[i]) for i in ((N_D, A_U, A_V) if al else (N_U, N_V, N_D, A_U, A_V)))
+
+
+@pytest.fixture(scope='module')
+def layouts():
+    return {name: make() for name, make in SCENES.items()}
+
+
+@pytest.mark.parametrize('name', sorted(SCENES))
+def test_layout(name, layouts, monkeypatch):
+    monkeypatch.delenv('MTSGPU_NO_SCAN_PAIRS', raising=False)
+    sc = layouts[name]
+    rec, n, npairs = scan_host(sc)
+    assert len(rec) == sum(n) <= 64
+    # every primitive once, but for the degenerate ones (only the tie scene's last)
+    want = list(range(sc.num_triangles - 1 if name == 'ties' else sc.num_triangles))
+    assert sorted(rec[:, PRIM].tolist()) == want
+    for g, grp in enumerate(_groups(rec, n)):
+        k, al = g // 2, bool(g % 2)
+        assert 2 * npairs[g] <= len(grp)
+        for r in grp:
+            assert int(r[K]) == k and _aligned(r) == al
+        for i in range(npairs[g]):
+            assert _key(grp[2 * i], al) == _key(grp[2 * i + 1], al)
+        singles = [_key(r, al) for r in grp[2 * npairs[g]:]]
+        assert len(set(singles)) == len(singles), 'two singles of group %d would pair' % g
+    # without pairs: the same records, no pair counts
+    monkeypatch.setenv('MTSGPU_NO_SCAN_PAIRS', '1')
+    rec0, n0, np0 = scan_host(sc)
+    assert np0 == [0] * 6 and n0 == n
+    assert sorted(map(bytes, rec0)) == sorted(map(bytes, rec))
+
+
+def test_pair_counts(layouts, monkeypatch):
+    monkeypatch.delenv('MTSGPU_NO_SCAN_PAIRS', raising=False)
+    rec, n, npairs = scan_host(layouts['C2'])
+    assert sum(n) == 32 and sum(npairs) >= 13, (n, npairs)
+    # the pentagon's fan: one pair and one single; the lone triangle and the light's quad
+    rec, n, npairs = scan_host(layouts['pentagon'])
+    where = {int(r[PRIM]): (g, i) for g, grp in enumerate(_groups(rec, n)) for i, r in enumerate(grp)}
+    g = where[0][0]
+    assert g % 2 == 0 and [where[p][0] for p in (0, 1, 2)] == [g] * 3
+    fan = sorted(where[p][1] for p in (0, 1, 2))
+    assert npairs[g] == 1 and fan[:2] == [0, 1] and fan[2] >= 2
+    assert sum(npairs) == 2 and where[4][0] == where[5][0] == 3      # the light: an aligned pair of axis y
+    assert where[3][1] >= 2 * npairs[where[3][0]]
+    rec, n, npairs = scan_host(layouts['one'])
+    assert sum(n) == 1 and sum(npairs) == 0
+    rec, n, npairs = scan_host(layouts['ties'])
+    assert sum(npairs) >= 2 * 5     # each block face is four coplanar records: two pairs
+    rec, n, npairs = scan_host(layouts['full'])
+    assert sum(npairs) >= 20        # the 19 quads and the light
