@@ -419,6 +419,24 @@ int mtsgpu_bvh_host(const mtsgpu_scene_desc *scene, uint32_t *nodes, size_t node
  * copied when `cap` (in words) suffices.  All counts are 0 for a scene the
  * kernels do not scan (more than 64 triangles, or analytic shapes). */
 int mtsgpu_scan_host(const mtsgpu_scene_desc *scene, float *records, size_t cap, uint32_t counts[12]);
+/* Host-only (no device needed): configure `scene` and export the unit face normal of
+ * every primitive as upload_scene forms it for scenes staged in LDS (3 floats each), with
+ * the primitive's three vertex positions (9 floats each); copied when prim_cap suffices. */
+int mtsgpu_face_normals_host(const mtsgpu_scene_desc *scene, float *normals, float *corners, size_t prim_cap,
+                             uint32_t *num_prims);
+/* Host-only (no device needed): the megakernel's item -> pixel arithmetic, run by the
+ * functions the kernels compile.  geom = {x0, y0, width, height, row_block, row_stride,
+ * row_phase, tile_shard, spp of the chunk, run shift, lanes of the grid}, width, height and
+ * lanes positive; for each pair
+ * (lane, round) of `lane_round`, round counting the items the lane has taken before,
+ * out[6i..] = {the lane has such an item, its sample of the chunk (may be >= spp: the
+ * missing sample of an odd tail), compact pixel, px, py, the item is rendered (a sample
+ * below spp at a pixel inside the window)}; info2 = {compact pixels, tiles across}. */
+int mtsgpu_index_host(const uint32_t geom[11], const uint32_t *lane_round, size_t n, uint32_t *out, uint32_t info2[2]);
+/* Host-only: sobol::look_up (sobolseq.h:93-125) for a film of resolution 2^m, 1 <= m <= 16,
+ * through the tables the kernels stage: out[i] = the sequence index of sample j at pixel
+ * (px, py), for the triples {px, py, j} of `px_py_j`. */
+int mtsgpu_lookup_host(uint32_t m, uint64_t scramble, const uint32_t *px_py_j, size_t n, uint64_t *out);
 /* Diagnostics (tests): device arithmetic probe -- for each i, out[8i..8i+7] =
  * {a/b, sqrt|a|, sin a, cos a, acos(clamp a), atan2(a,b), exp(-|a|), a*b+a}
  * computed by the kernels' own routines; scene info = {nodes, prims, depth, CUs}. */

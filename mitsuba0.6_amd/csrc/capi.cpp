@@ -89,6 +89,8 @@ struct mtsgpu_ctx {
     MtsgDeviceScene dscene;
     DevBuf scan_tris;   // k-grouped TriAccel records of scan-sized scenes
     uint32_t scan_n[6] = {0, 0, 0, 0, 0, 0};   // as MtsgLaunch::scan_n: records | plane pairs << 16
+    uint32_t one_emitter = 0;   // the uploaded emitter CDF is {0.0f, 1.0f} bit for bit (MtsgLaunch::one_emitter)
+    DevBuf face_n;   // unit face normals per primitive (MtsgLaunch::face_n)
     DevBuf nodes, hnodes, tris, prim_vtx, dpdu, positions, normals, shapes, bsdfs, emitters, area_cdf, em_cdf, sobol;
     DevBuf env, env_texels, env_rows, env_cols, env_weights, env_grows, env_gcols;
     DevBuf rtrans, texcoords, analytic;
@@ -108,7 +110,38 @@ struct mtsgpu_ctx {
     unsigned long long last_counters[16] = {};
 };
 
+// Every object that takes an MtsgLaunch by value reports the size it was compiled with.  A
+// library linked from objects of two layouts (a stale object after layout.h changed) would
+// hand its kernels a misread launch record: refuse to run instead.
+extern "C" {
+uint32_t mtsg_launch_bytes_path_kernel();
+uint32_t mtsg_launch_bytes_wf_kernel();
+#define MTSG_BYTES_DECL(N) uint32_t mtsg_launch_bytes_path_f##N(); uint32_t mtsg_launch_bytes_wf_shade_f##N();
+MTSG_BYTES_DECL(0) MTSG_BYTES_DECL(1) MTSG_BYTES_DECL(2) MTSG_BYTES_DECL(3) MTSG_BYTES_DECL(6) MTSG_BYTES_DECL(7)
+#undef MTSG_BYTES_DECL
+}
+
 namespace {
+
+// empty when every object agrees with this one on sizeof(MtsgLaunch), else what differs
+const std::string &launch_layout_error() {
+    static const std::string msg = [] {
+        std::string m;
+        const uint32_t mine = (uint32_t)sizeof(MtsgLaunch);
+        const struct { const char *name; uint32_t bytes; } objs[] = {
+            {"path_kernel", mtsg_launch_bytes_path_kernel()}, {"wf_kernel", mtsg_launch_bytes_wf_kernel()},
+#define MTSG_BYTES_ROW(N) {"path_f" #N, mtsg_launch_bytes_path_f##N()}, {"wf_shade_f" #N, mtsg_launch_bytes_wf_shade_f##N()},
+            MTSG_BYTES_ROW(0) MTSG_BYTES_ROW(1) MTSG_BYTES_ROW(2) MTSG_BYTES_ROW(3) MTSG_BYTES_ROW(6) MTSG_BYTES_ROW(7)
+#undef MTSG_BYTES_ROW
+        };
+        for (const auto &o : objs)
+            if (o.bytes != mine)
+                m += std::string(m.empty() ? "libmtsgpu.so mixes launch-record layouts (rebuild from clean): " : ", ") +
+                     o.name + ".o has " + std::to_string(o.bytes) + " bytes, capi.o " + std::to_string(mine);
+        return m;
+    }();
+    return msg;
+}
 
 int ensure_kdtree(mtsgpu_ctx *ctx);   // the reference's SAH kd-tree, built on first use (below)
 
@@ -161,6 +194,10 @@ int mtsgpu_abi_version(void) { return MTSGPU_ABI_VERSION; }
 int mtsgpu_create(int device, mtsgpu_ctx **out) {
     if (!out) return MTSGPU_EINVAL;
     *out = nullptr;
+    if (!launch_layout_error().empty()) {   // before anything can be launched
+        g_create_error = launch_layout_error();
+        return MTSGPU_ESTATE;
+    }
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0) {
@@ -254,7 +291,8 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     hipStream_t s = ctx->stream;
     if ((e = upload(ctx->nodes, H.nodes, s)) != hipSuccess || (e = upload(ctx->hnodes, H.hnodes, s)) != hipSuccess ||
         (e = upload(ctx->tris, H.tris, s)) != hipSuccess ||
-        (e = upload(ctx->prim_vtx, H.prim_vtx, s)) != hipSuccess || (e = upload(ctx->dpdu, H.dpdu, s)) != hipSuccess ||
+        (e = upload(ctx->prim_vtx, H.prim_vtx, s)) != hipSuccess || (e = upload(ctx->face_n, H.face_n, s)) != hipSuccess ||
+        (e = upload(ctx->dpdu, H.dpdu, s)) != hipSuccess ||
         (e = upload(ctx->positions, H.positions, s)) != hipSuccess || (e = upload(ctx->normals, H.normals, s)) != hipSuccess ||
         (e = upload(ctx->shapes, H.shapes, s)) != hipSuccess || (e = upload(ctx->bsdfs, H.bsdfs, s)) != hipSuccess ||
         (e = upload(ctx->emitters, H.emitters, s)) != hipSuccess || (e = upload(ctx->area_cdf, H.area_cdf, s)) != hipSuccess ||
@@ -322,6 +360,12 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     D.analytic = H.analytic.empty() ? nullptr : (const MtsgAnalytic *)ctx->analytic.p;
     for (int a = 0; a < 3; ++a) { D.aabb_min[a] = H.aabb_min[a]; D.aabb_max[a] = H.aabb_max[a]; }
     D.cam = H.cam;
+    // a launch constant of the scene: sampleReuse over the CDF {0, 1} is the identity (dpath.h shade)
+    {
+        uint32_t w[2] = {1u, 0u};
+        if (H.em_cdf.size() == 2) std::memcpy(w, H.em_cdf.data(), 8);
+        ctx->one_emitter = (H.emitters.size() == 1 && w[0] == 0u && w[1] == 0x3f800000u) ? 1u : 0u;
+    }
     ctx->have_scene = true;
     return MTSGPU_OK;
 }
@@ -620,10 +664,34 @@ static uint32_t run_shift(const MtsgLaunch &L, uint64_t lanes) {
     return s;
 }
 
+// the window's work decomposition: compact rows (interleave) x columns in 8x8 tiles, or
+// (tile shards) every row_stride-th 8x8 tile of the window; with the reciprocals the
+// kernels divide by (layout.h pixel_of)
+static void launch_geometry(MtsgLaunch &L, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t row_block,
+                            uint32_t row_stride, uint32_t row_phase, bool tile_shard) {
+    L.x0 = x0; L.y0 = y0; L.width = width; L.height = height;
+    L.row_block = row_block ? row_block : 1;
+    L.row_stride = row_stride ? row_stride : 1;
+    L.row_phase = row_phase % L.row_stride;
+    L.tile_shard = tile_shard ? 1u : 0u;
+    L.tiles_x = (width + 7) / 8;
+    if (L.tile_shard) {
+        const uint64_t tiles = (uint64_t)L.tiles_x * ((height + 7) / 8);
+        L.num_pixels = (uint32_t)((tiles + L.row_stride - 1) / L.row_stride * 64);
+    } else {
+        const uint32_t rowsCompact =
+            ((height + L.row_block - 1) / L.row_block + L.row_stride - 1) / L.row_stride * L.row_block;
+        const uint32_t tilesY = (rowsCompact + 7) / 8;
+        L.num_pixels = L.tiles_x * tilesY * 64;
+    }
+    mtsg_launch_index(L, 0);   // the reciprocals; the megakernel's grid is known per chunk (render_impl)
+}
+
 static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *film_host, float *film_dev,
                        float *samples_host, hipStream_t stream, mtsgpu_stats *stats) {
     if (!ctx || !P) return MTSGPU_EINVAL;
     if (!ctx->have_scene) return fail(ctx, MTSGPU_ESTATE, "render called before a successful upload_scene");
+    if (!launch_layout_error().empty()) return fail(ctx, MTSGPU_ESTATE, launch_layout_error());
     if (P->spp == 0) return fail(ctx, MTSGPU_EINVAL, "sampleCount must be positive");
     const bool pathLike = P->integrator == MTSGPU_INTEGRATOR_PATH || P->integrator == MTSGPU_INTEGRATOR_VOLPATH;
     if (pathLike && P->rr_depth <= 0)
@@ -668,23 +736,10 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     L.film_h = (int)H.film_h;
     L.fw = (int)H.film_w + 2 * L.filter.border;
     L.fh = (int)H.film_h + 2 * L.filter.border;
-    L.x0 = P->x0; L.y0 = P->y0; L.width = P->width; L.height = P->height;
-    L.row_block = P->row_block ? P->row_block : 1;
-    L.row_stride = P->row_stride ? P->row_stride : 1;
-    L.row_phase = P->row_phase % L.row_stride;
-    // work decomposition: compact rows (interleave) x columns in 8x8 tiles, or
-    // (MTSGPU_FLAG_TILE_SHARD) every row_stride-th 8x8 tile of the window
-    L.tile_shard = (P->flags & MTSGPU_FLAG_TILE_SHARD) ? 1u : 0u;
-    L.tiles_x = (P->width + 7) / 8;
-    if (L.tile_shard) {
-        const uint64_t tiles = (uint64_t)L.tiles_x * ((P->height + 7) / 8);
-        L.num_pixels = (uint32_t)((tiles + L.row_stride - 1) / L.row_stride * 64);
-    } else {
-        const uint32_t rowsCompact =
-            ((P->height + L.row_block - 1) / L.row_block + L.row_stride - 1) / L.row_stride * L.row_block;
-        const uint32_t tilesY = (rowsCompact + 7) / 8;
-        L.num_pixels = L.tiles_x * tilesY * 64;
-    }
+    launch_geometry(L, P->x0, P->y0, P->width, P->height, P->row_block, P->row_stride, P->row_phase,
+                    (P->flags & MTSGPU_FLAG_TILE_SHARD) != 0);
+    L.one_emitter = std::getenv("MTSGPU_NO_ONE_EMITTER") ? 0u : ctx->one_emitter;
+    L.face_n = (const float *)ctx->face_n.p;
     // Sobol index width: frame << 2m | 2m bits (sobolseq.h:93-125); 52 columns per dimension
     // the direct integrator's 2D sample arrays index the Sobol sequence at spp x count
     const bool direct = P->integrator == MTSGPU_INTEGRATOR_DIRECT;
@@ -716,7 +771,7 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     L.num_verts = (uint32_t)(H.positions.size() / 3);
     L.num_shapes = (uint32_t)H.shapes.size();
     const size_t sceneBytes = H.nodes.size() * sizeof(MtsgNode) + H.tris.size() * sizeof(MtsgTri) +
-                              H.prim_vtx.size() * 4 + H.dpdu.size() * 4 + H.positions.size() * 4 +
+                              H.prim_vtx.size() * 4 + H.dpdu.size() * 4 + H.face_n.size() * 4 + H.positions.size() * 4 +
                               H.normals.size() * 4 + H.shapes.size() * sizeof(MtsgShape);
     L.scene_lds = (sceneBytes <= (32u << 10) && !std::getenv("MTSGPU_NO_SCENE_LDS")) ? 1u : 0u;
     L.scan = (L.scene_lds && H.tris.size() <= MTSG_SCAN_MAX && H.analytic.empty() && !std::getenv("MTSGPU_NO_SCAN"))
@@ -776,7 +831,7 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     L.waves = 3;
     if (!L.scene_lds) {
         const size_t perBlock = (160u << 10) / 4;
-        const size_t fixed = ((size_t)L.stack_depth * 3 * BLOCK_THREADS + 1) / 2 * 4 + 16 * 16 * 4;
+        const size_t fixed = ((size_t)L.stack_depth * 3 * BLOCK_THREADS + 1) / 2 * 4 + MTSG_LUT_WORDS * 4;
         if (fixed < perBlock) {
             L.waves = 4;
             L.lds_dims = (uint32_t)std::min<size_t>(32, (perBlock - fixed) / ((size_t)L.nibbles * 16 * 4));
@@ -948,6 +1003,7 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
             if (replay && (uint64_t)grid * 256 < L.units)
                 return fail(ctx, MTSGPU_EINVAL, "SFMT replay: more 32x32 blocks than resident lanes (crop too large)");
             L.round_shift = run_shift(L, (uint64_t)grid * BLOCK_THREADS);
+            mtsg_launch_index(L, (uint64_t)grid * BLOCK_THREADS);
             if ((e = mtsg_launch_path(L, grid, nsamp != 0, stats_mode, stream)) != hipSuccess) return hip_fail(ctx, e, "path kernel launch");
         }
         if ((e = L.gather ? mtsg_launch_gather(L, stream) : mtsg_launch_reduce(L, stream)) != hipSuccess)
@@ -1061,7 +1117,7 @@ const char *mtsgpu_last_error(mtsgpu_ctx *ctx) { return ctx ? ctx->err.c_str() :
 void mtsgpu_destroy(mtsgpu_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    DevBuf *bufs[] = {&ctx->scan_tris, &ctx->kd_nodes, &ctx->kd_indices, &ctx->kd_tris, &ctx->nodes, &ctx->hnodes, &ctx->tris, &ctx->prim_vtx, &ctx->dpdu, &ctx->positions, &ctx->normals,
+    DevBuf *bufs[] = {&ctx->face_n, &ctx->scan_tris, &ctx->kd_nodes, &ctx->kd_indices, &ctx->kd_tris, &ctx->nodes, &ctx->hnodes, &ctx->tris, &ctx->prim_vtx, &ctx->dpdu, &ctx->positions, &ctx->normals,
                       &ctx->shapes, &ctx->bsdfs, &ctx->emitters, &ctx->area_cdf, &ctx->em_cdf, &ctx->sobol,
                       &ctx->film_own, &ctx->film_spill, &ctx->samples, &ctx->counters, &ctx->contrib,
                       &ctx->env, &ctx->env_texels, &ctx->env_rows, &ctx->env_cols, &ctx->env_weights, &ctx->env_grows, &ctx->env_gcols,
@@ -1181,6 +1237,74 @@ int mtsgpu_scan_host(const mtsgpu_scene_desc *scene, float *records, size_t cap,
     std::vector<MtsgTri> g;
     mtsg_scan_layout(H.tris, g, counts, counts + 6);
     if (records && cap >= g.size() * 12) std::memcpy(records, g.data(), g.size() * sizeof(MtsgTri));
+    return MTSGPU_OK;
+}
+
+// the per-primitive unit face normals upload_scene forms for LDS scenes (scene_build.cpp
+// mtsg_face_normal), with the vertex positions they were formed from (9 floats per primitive)
+int mtsgpu_face_normals_host(const mtsgpu_scene_desc *scene, float *normals, float *corners, size_t prim_cap,
+                             uint32_t *num_prims) {
+    if (!scene || !num_prims) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    const int rc = mtsg_configure_scene(scene, H, err);
+    if (rc) return rc;
+    const size_t n = H.face_n.size() / 3;
+    *num_prims = (uint32_t)n;
+    if (!normals || !corners || prim_cap < n) return MTSGPU_OK;
+    std::memcpy(normals, H.face_n.data(), n * 3 * sizeof(float));
+    for (size_t p = 0; p < n; ++p)
+        for (int v = 0; v < 3; ++v)
+            for (int k = 0; k < 3; ++k)
+                corners[9 * p + 3 * v + k] = H.positions[3 * (size_t)H.prim_vtx[4 * p + v] + k];
+    return MTSGPU_OK;
+}
+
+// geom = {x0, y0, width, height, row_block, row_stride, row_phase, tile_shard, chunk_spp,
+// round_shift, lanes}: the launch's index constants as render_impl forms them, then for each
+// (lane, round) the megakernel's own stepping (layout.h mtsg_run_init / mtsg_run_step, pixel_of)
+int mtsgpu_index_host(const uint32_t geom[11], const uint32_t *lane_round, size_t n, uint32_t *out, uint32_t info2[2]) {
+    if (!geom || (n && (!lane_round || !out))) return MTSGPU_EINVAL;
+    MtsgLaunch L;
+    std::memset(&L, 0, sizeof L);
+    launch_geometry(L, geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7] != 0);
+    L.chunk_spp = geom[8];
+    L.round_shift = geom[9];
+    if (!L.num_pixels || !geom[10] || L.round_shift > 6) return MTSGPU_EINVAL;
+    mtsg_launch_index(L, geom[10]);
+    if (info2) { info2[0] = L.num_pixels; info2[1] = L.tiles_x; }
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t g = lane_round[2 * i], target = lane_round[2 * i + 1];
+        uint32_t *o = out + 6 * i;
+        uint32_t round, pix, jj = 0;
+        mtsg_run_init(L, g, round, pix);
+        bool more = true;
+        for (uint32_t k = 0; k <= target && more; ++k) more = mtsg_run_step(L, round, pix, jj);
+        int px = 0, py = 0;
+        const bool valid = more && jj < L.chunk_spp && pixel_of(L, pix, px, py);
+        o[0] = more ? 1u : 0u;
+        o[1] = more ? jj : 0u;
+        o[2] = more ? pix : 0u;
+        o[3] = valid ? (uint32_t)px : 0u;
+        o[4] = valid ? (uint32_t)py : 0u;
+        o[5] = valid ? 1u : 0u;
+    }
+    return MTSGPU_OK;
+}
+
+// sobol::look_up for film resolution 2^m through the tables the kernels stage
+// (layout.h mtsg_lut_word, sobol_lookup_lds): out[i] = the index of sample j at pixel (px, py)
+int mtsgpu_lookup_host(uint32_t m, uint64_t scramble, const uint32_t *px_py_j, size_t n, uint64_t *out) {
+    if (m < 1 || m > 16 || (n && (!px_py_j || !out))) return MTSGPU_EINVAL;
+    MtsgLookup lut;
+    mtsg_sobol_lookup_solve(m, lut);
+    uint32_t tab[MTSG_LUT_WORDS];
+    for (uint32_t i = 0; i < MTSG_LUT_WORDS; ++i) tab[i] = mtsg_lut_word(lut, i);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t j = px_py_j[3 * i + 2];
+        const uint32_t nibbles = ((uint64_t)j << (2 * m)) >> 32 ? MTSG_NIBBLES : 8;   // as render_impl: 8 while the index fits 32 bits
+        out[i] = sobol_lookup_lds(lut, (const uint32_t *)tab, nibbles, j, px_py_j[3 * i], px_py_j[3 * i + 1], scramble);
+    }
     return MTSGPU_OK;
 }
 

@@ -9,8 +9,8 @@
 //  * a lane whose path ends starts its next item immediately (regeneration);
 //  * each loop iteration traces the lane's pending shadow ray and its
 //    closest-hit ray, then shades (PathShader, dpath.h);
-//  * LDS holds the Sobol tables and the lane-strided traversal stacks (and
-//    the whole scene for small ones).
+//  * LDS holds the Sobol and look_up tables and the lane-strided traversal stacks
+//    (and the whole scene, with its triangles' unit face normals, for small ones).
 #pragma once
 #include "dpath.h"
 
@@ -53,10 +53,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     PathCounters c = {};   // INSTR statistics only: the always-on counts are wave-uniform (wc)
     WaveCounters wc = {};
 
-    // static striding: lane g takes sample runs g + k * lanes, k = 0, 1, ... (`round`
-    // counts the lane's samples, or the SFMT replay's position in its unit: 32 bits,
-    // not a 64-bit item index, live across the bounce loop)
-    const uint64_t lanes = (uint64_t)gridDim.x * BLOCK;
+    // static striding: lane g takes sample runs g + k * lanes, k = 0, 1, ... (`round` is
+    // the carried run state of layout.h mtsg_run_step, or the SFMT replay's position in
+    // its unit: 32 bits, not a 64-bit item index, live across the bounce loop)
     const uint32_t g = xcd_block(L.xcds) * BLOCK + threadIdx.x;
     uint32_t round = 0;
     bool done = false;
@@ -64,6 +63,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     PathState st;
     st.active = false;
     st.pix = 0;
+    if (!L.replay) mtsg_run_init(L, g, round, st.pix);   // the lane's one division
     st.smp.sobolIndex = 0; st.smp.sampleIndex = 0; st.smp.dim = 0; st.smp.err = false;
     st.sx = st.sy = 0;
     st.haveRay = st.primary = st.haveShadow = false;
@@ -102,13 +102,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
             // k * 2^s .. of one pixel back to back (run q = g + r * lanes; s = L.round_shift):
             // a box-filter record sector (film_slot: samples 2k, 2k + 1) has both halves
             // stored one path apart, while the line is still in this XCD's L2, and the
-            // wave's primary rays revisit the same pixels
-            const uint32_t rs = L.round_shift;
-            const uint64_t q = g + (uint64_t)(round >> rs) * lanes;
-            const uint32_t jq = (uint32_t)(q / L.num_pixels), jr = jq << rs, jj = jr + (round & ((1u << rs) - 1u));
-            if (jr >= L.chunk_spp) { done = true; break; }
-            ++round;
-            if (jj < L.chunk_spp) sh.start_jp(st, jj, (uint32_t)(q - (uint64_t)jq * L.num_pixels));
+            // wave's primary rays revisit the same pixels.  (q / num_pixels, q % num_pixels)
+            // is carried from run to run in `round` and st.pix (layout.h mtsg_run_step):
+            // no division here
+            uint32_t jj;
+            if (!mtsg_run_step(L, round, st.pix, jj)) { done = true; break; }
+            if (jj < L.chunk_spp) sh.start_jp(st, jj, st.pix);
         }
         if (__all(done)) break;
         MK_STAMP(mkT[0], mkT0);

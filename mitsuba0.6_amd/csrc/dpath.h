@@ -795,7 +795,9 @@ typedef __attribute__((address_space(1))) const MtsgShape glb_shape;
 typedef __attribute__((address_space(3))) const MtsgShape lds_shape;
 template <bool INLDS> struct HitSrc;
 template <> struct HitSrc<false> { glb_u32 *pv; glb_f32 *pos, *nrm, *dpdu; glb_shape *shapes; };
-template <> struct HitSrc<true> { lds_u32 *pv; lds_f32 *pos, *nrm, *dpdu; lds_shape *shapes; };
+// (LDS scenes also stage the primitives' unit face normals, fn: a constant of the triangle
+// that fill_hit and the area-light sample would otherwise re-form, ~45 VALU each)
+template <> struct HitSrc<true> { lds_u32 *pv; lds_f32 *pos, *nrm, *dpdu, *fn; lds_shape *shapes; };
 template <typename P> __device__ __forceinline__ f3 ldp3(P p) { return mk(p[0], p[1], p[2]); }
 
 // fillIntersectionRecord<true> (skdtree.h:343-429); UV = TEX
@@ -825,10 +827,15 @@ __device__ __forceinline__ void fill_hit(const MtsgDeviceScene &S, const HS &hs,
     const f3 p0 = ldp3(hs.pos + 3 * (size_t)pv.x), p1 = ldp3(hs.pos + 3 * (size_t)pv.y),
              p2 = ldp3(hs.pos + 3 * (size_t)pv.z);
     h.p = add(add(mul(p0, bx), mul(p1, by)), mul(p2, bz));
-    const f3 side1 = sub(p1, p0), side2 = sub(p2, p0);
-    f3 faceNormal = cross(side1, side2);
-    const float length = len(faceNormal);
-    if (!is_zero(faceNormal)) faceNormal = divs(faceNormal, length);
+    f3 faceNormal;
+    if constexpr (std::is_same<HS, HitSrc<true>>::value) {
+        faceNormal = ldp3(hs.fn + 3 * (size_t)prim);   // the same operations, done by the host (mtsg_face_normal)
+    } else {
+        const f3 side1 = sub(p1, p0), side2 = sub(p2, p0);
+        faceNormal = cross(side1, side2);
+        const float length = len(faceNormal);
+        if (!is_zero(faceNormal)) faceNormal = divs(faceNormal, length);
+    }
     const f3 dpdu = ldp3(hs.dpdu + 3 * (size_t)prim);
     f3 shN;
     if (hs.shapes[h.shape].has_normals) {
@@ -1084,51 +1091,13 @@ __device__ __noinline__ EnvSample const_sample_direct(glb_env *E, f3 ref, f3 ref
     return r;
 }
 
-// compact pixel index (8x8 tiles over the window's active rows, or the
-// window's every row_stride-th tile) -> image pixel
-__device__ __forceinline__ bool pixel_of(const MtsgLaunch &L, uint32_t p, int &px, int &py) {
-    const uint32_t tile = p >> 6, in = p & 63;
-    if (L.tile_shard) {
-        const uint32_t t = tile * L.row_stride + L.row_phase;
-        const uint32_t lx = (t % L.tiles_x) * 8 + (in & 7), ly = (t / L.tiles_x) * 8 + (in >> 3);
-        if (lx >= L.width || ly >= L.height) return false;
-        px = (int)(L.x0 + lx);
-        py = (int)(L.y0 + ly);
-        return true;
-    }
-    const uint32_t lx = (tile % L.tiles_x) * 8 + (in & 7);
-    const uint32_t r = (tile / L.tiles_x) * 8 + (in >> 3);
-    if (lx >= L.width) return false;
-    const uint32_t blk = r / L.row_block, off = r % L.row_block;
-    const uint32_t ly = (blk * L.row_stride + L.row_phase) * L.row_block + off;
-    if (ly >= L.height) return false;
-    px = (int)(L.x0 + lx);
-    py = (int)(L.y0 + ly);
-    return true;
-}
+// (pixel_of, the compact pixel index -> image pixel rule, is shared with the host: layout.h)
 
 #ifndef MTSG_WAVES_PER_EU
 #define MTSG_WAVES_PER_EU 3
 #endif
 
-// sobol::look_up (sobolseq.h:93-125) as the GF(2) solve it encodes; the XOR of
-// the second dimension's (top m bits of) columns over the index bits comes from
-// 4-bit tables in LDS (ycolTab[c][v]), the m x m inverse from the kernel args
-template <typename T>
-__device__ __forceinline__ uint64_t sobol_lookup_lds(const MtsgLookup &Lu, T *ycolTab, uint32_t nibbles,
-                                                     uint32_t frame, uint32_t px, uint32_t py, uint64_t scramble) {
-    const uint32_t m = Lu.m;
-    const uint32_t s = (uint32_t)((scramble & 0xFFFFFFFFull) >> (32 - m));
-    const uint32_t mask = (1u << m) - 1u;
-    const uint32_t sx = (px ^ s) & mask, sy = (py ^ s) & mask;
-    const uint32_t jlo = __builtin_bitreverse32(sx) >> (32 - m);
-    const uint64_t index = ((uint64_t)frame << (2 * m)) | jlo;
-    const uint32_t K = (nibbles == 8) ? sobol_bits<8>(ycolTab, index) : sobol_bits<MTSG_NIBBLES>(ycolTab, index);
-    const uint32_t rhs = (sy ^ K) & mask;
-    uint32_t jhi = 0;
-    for (uint32_t t = 0; t < m; ++t) jhi |= (uint32_t)(__builtin_popcount(Lu.inv[t] & rhs) & 1) << t;
-    return index | ((uint64_t)jhi << m);
-}
+// (sobol_lookup_lds, sobol::look_up through the folded tables in LDS, is shared with the host: layout.h)
 
 // ---------------------------------------------------------------------------
 // Li() as a per-path state machine, one bounce per step.  One step traces the
@@ -1169,7 +1138,7 @@ struct PathCounters {
     unsigned long long nodes, tests, hits, nee, sobol;
 };
 
-// LDS of path_kernel / wf_shade: [Sobol nibble tables][look_up column tables]
+// LDS of path_kernel / wf_shade: [Sobol nibble tables][look_up tables (MTSG_LUT_WORDS, layout.h)]
 // [BVH + TriAccel + hit data (SCENE_LDS)][traversal stacks]
 template <bool SCENE_LDS>
 struct LdsView {
@@ -1184,6 +1153,12 @@ struct LdsView {
 template <bool SCENE_LDS>
 __device__ __forceinline__ LdsView<SCENE_LDS> lds_view(const MtsgLaunch &L, uint32_t *lds);
 
+// the look_up tables (layout.h sobol_lookup_lds), formed once per block: the inverse is
+// applied here, not per look-up
+__device__ __forceinline__ void stage_lut(const MtsgLaunch &L, uint32_t *tab) {
+    for (uint32_t i = threadIdx.x; i < MTSG_LUT_WORDS; i += BLOCK) tab[i] = mtsg_lut_word(L.lut, i);
+}
+
 template <bool SCENE_LDS>
 __device__ __forceinline__ LdsView<SCENE_LDS> stage_lds(const MtsgLaunch &L, uint32_t *lds) {
     const MtsgDeviceScene &S = L.scene;
@@ -1192,14 +1167,8 @@ __device__ __forceinline__ LdsView<SCENE_LDS> stage_lds(const MtsgLaunch &L, uin
         const uint32_t d = i / (L.nibbles * 16), r = i % (L.nibbles * 16);
         lds[i] = L.sobol_nib[(size_t)d * MTSG_NIBBLES * 16 + r];
     }
-    for (uint32_t i = threadIdx.x; i < 16 * 16; i += BLOCK) {
-        const uint32_t c = i >> 4, v = i & 15;
-        uint32_t r = 0;
-        for (int b = 0; b < 4; ++b)
-            if ((v >> b) & 1) r ^= L.lut.ycol[4 * c + b];
-        lds[tabWords + i] = r;
-    }
-    const uint32_t base2 = tabWords + 16 * 16;
+    stage_lut(L, lds + tabWords);
+    const uint32_t base2 = tabWords + MTSG_LUT_WORDS;
     uint32_t sceneWords = 0;
     if (SCENE_LDS) {
         const uint32_t nodeWords = L.num_nodes * 16, triWords = S.num_prims * 12;
@@ -1208,14 +1177,15 @@ __device__ __forceinline__ LdsView<SCENE_LDS> stage_lds(const MtsgLaunch &L, uin
         for (uint32_t i = threadIdx.x; i < nodeWords; i += BLOCK) lds[base2 + i] = gn[i];
         for (uint32_t i = threadIdx.x; i < triWords; i += BLOCK) lds[base2 + nodeWords + i] = gt[i];
         sceneWords = nodeWords + triWords;
-        // the vertices' triangle data: prim_vtx, dpdu, positions, normals, shape records
+        // the vertices' triangle data: prim_vtx, dpdu, face normals, positions, normals, shape records
         const uint32_t np = S.num_prims, nv = L.num_verts, ns = L.num_shapes * (sizeof(MtsgShape) / 4);
-        const uint32_t *srcs[5] = {S.prim_vtx, reinterpret_cast<const uint32_t *>(S.dpdu),
+        const uint32_t *srcs[6] = {S.prim_vtx, reinterpret_cast<const uint32_t *>(S.dpdu),
+                                   reinterpret_cast<const uint32_t *>(L.face_n),
                                    reinterpret_cast<const uint32_t *>(S.positions),
                                    reinterpret_cast<const uint32_t *>(S.normals),
                                    reinterpret_cast<const uint32_t *>(S.shapes)};
-        const uint32_t lens[5] = {4 * np, 3 * np, 3 * nv, 3 * nv, ns};
-        for (int a = 0; a < 5; ++a) {
+        const uint32_t lens[6] = {4 * np, 3 * np, 3 * np, 3 * nv, 3 * nv, ns};
+        for (int a = 0; a < 6; ++a) {
             for (uint32_t i = threadIdx.x; i < lens[a]; i += BLOCK) lds[base2 + sceneWords + i] = srcs[a][i];
             sceneWords += lens[a];
         }
@@ -1231,10 +1201,10 @@ template <bool SCENE_LDS>
 __device__ __forceinline__ LdsView<SCENE_LDS> lds_view(const MtsgLaunch &L, uint32_t *lds) {
     const MtsgDeviceScene &S = L.scene;
     const uint32_t tabWords = L.lds_dims * L.nibbles * 16;
-    const uint32_t base2 = tabWords + 16 * 16;
+    const uint32_t base2 = tabWords + MTSG_LUT_WORDS;
     uint32_t sceneWords = 0;
     if (SCENE_LDS) {
-        sceneWords = L.num_nodes * 16 + S.num_prims * 12 + 4 * S.num_prims + 3 * S.num_prims + 3 * L.num_verts +
+        sceneWords = L.num_nodes * 16 + S.num_prims * 12 + 4 * S.num_prims + 6 * S.num_prims + 3 * L.num_verts +
                      3 * L.num_verts + L.num_shapes * (uint32_t)(sizeof(MtsgShape) / 4);
     }
     LdsView<SCENE_LDS> v;
@@ -1248,9 +1218,10 @@ __device__ __forceinline__ LdsView<SCENE_LDS> lds_view(const MtsgLaunch &L, uint
         lds_u32 *b = (lds_u32 *)(lds + base2 + L.num_nodes * 16 + np * 12);
         v.hs.pv = b;
         v.hs.dpdu = (lds_f32 *)(b + 4 * np);
-        v.hs.pos = (lds_f32 *)(b + 7 * np);
-        v.hs.nrm = (lds_f32 *)(b + 7 * np + 3 * nv);
-        v.hs.shapes = (lds_shape *)(b + 7 * np + 6 * nv);
+        v.hs.fn = (lds_f32 *)(b + 7 * np);
+        v.hs.pos = (lds_f32 *)(b + 10 * np);
+        v.hs.nrm = (lds_f32 *)(b + 10 * np + 3 * nv);
+        v.hs.shapes = (lds_shape *)(b + 10 * np + 6 * nv);
     } else {
         v.hs.pv = (glb_u32 *)S.prim_vtx;
         v.hs.dpdu = (glb_f32 *)S.dpdu;
@@ -1519,8 +1490,12 @@ struct PathShader {
                         // Scene::sampleEmitterDirect (scene.cpp:828-852)
                         float ex, ey;
                         next2d(SC, L.resolution, smp, px, py, ex, ey);
-                        float emPdf;
-                        const uint32_t ei = dd_sample_reuse(S.em_cdf, S.num_emitters, ex, &emPdf);
+                        // one emitter whose CDF is {0.0f, 1.0f} (L.one_emitter, checked at upload):
+                        // sampleReuse returns emitter 0 with pdf 1 - 0 and leaves ex = (ex - 0) / 1
+                        float emPdf = 1.0f;
+                        uint32_t ei = 0;
+                        const bool oneEm = L.one_emitter != 0;
+                        if (!oneEm) ei = dd_sample_reuse(S.em_cdf, S.num_emitters, ex, &emPdf);
                         if (STATS) c.nee++;
                         const MtsgEmitter &e = S.emitters[ei];
                         f3 value = mk(0, 0, 0), dd = mk(0, 0, 1);
@@ -1562,7 +1537,12 @@ struct PathShader {
                                      n2 = ldp3(hs.nrm + 3 * (size_t)pv.z);
                             ln = normalize(add(add(mul(n0, 1.0f - bx - by), mul(n1, bx)), mul(n2, by)));
                         } else {
-                            ln = normalize(cross(sideA, sideB));
+                            // the staged face normal is normalize(cross(sideA, sideB)) by the same
+                            // operations, except that an all-zero cross stays zero there
+                            // (fill_hit's guard) where normalize gives NaN: that case keeps this code
+                            ln = mk(0, 0, 0);
+                            if constexpr (SCENE_LDS) ln = ldp3(hs.fn + 3 * (size_t)prim);
+                            if (is_zero(ln)) ln = normalize(cross(sideA, sideB));
                         }
                         pdf = e.inv_area;
                         // Shape::sampleDirect (shape.cpp:102-115)
@@ -1578,8 +1558,11 @@ struct PathShader {
                         }
                         if (pdf != 0) {
                             // the NEE estimate but for visibility (path.cpp:176-199)
-                            const float dpdf = pdf * emPdf;
-                            value = divs(value, emPdf);
+                            float dpdf = pdf;   // pdf * 1 and value / 1 are pdf and value
+                            if (!oneEm) {
+                                dpdf = pdf * emPdf;
+                                value = divs(value, emPdf);
+                            }
                             f3 c = mk(0, 0, 0);
                             if (!is_zero(value)) {
                                 const f3 wo = to_local(P.its.sh, dd);

@@ -339,6 +339,14 @@ struct MtsgLaunch {
     float *samples;                   // optional per-sample records
     unsigned long long *counters;     // [0] samples [1] rays [2] shadow [3] pathlen [4] nodes [5] tests
                                       // [6] dim errors [7] hits [9] nee [10] sobol words
+    // launch constants of the item -> pixel arithmetic (mtsg_launch_index, below): the kernels
+    // divide by tiles_x and row_block with one multiply-high and one correction (mtsg_divmod),
+    // and the megakernel carries (sample run, compact pixel) from run to run (mtsg_run_step)
+    uint32_t tiles_x_rcp, row_block_rcp;   // floor(2^32 / d); 2^32 - 1 for d = 1
+    uint32_t run_dq, run_dr;               // lanes / num_pixels and lanes % num_pixels of the megakernel's grid
+    uint32_t one_emitter;                  // the emitter CDF is {0.0f, 1.0f} bit for bit: emitter 0 with pdf 1
+    const float *face_n;                   // 3 per primitive: unit face normals, staged in LDS with a small scene
+                                           // (HitSrc<true>::fn; scene_build.cpp mtsg_face_normal)
 };
 
 #ifndef MTSG_MIN_RUNS
@@ -346,3 +354,138 @@ struct MtsgLaunch {
 #endif
 
 #define MTSG_NIBBLES 13
+
+// ---------------------------------------------------------------------------
+// Index arithmetic the kernels and the host share (capi.cpp mtsgpu_index_host
+// runs these very functions): item -> (sample, compact pixel) -> image pixel,
+// and sobol::look_up through folded tables.
+// ---------------------------------------------------------------------------
+#if defined(__HIPCC__) || defined(__HIP__)
+#define MTSG_HD __host__ __device__ __forceinline__
+#else
+#define MTSG_HD inline
+#endif
+
+// n / d and n % d by rcp = floor(2^32 / d) (2^32 - 1 for d = 1), exact for every 32-bit n
+// and every d >= 1: n * rcp / 2^32 lies in (n / d - 1, n / d], so its floor is the quotient
+// or one less, and one correction by the remainder settles it
+MTSG_HD uint32_t mtsg_rcp32(uint32_t d) { return d <= 1u ? 0xffffffffu : (uint32_t)(0x100000000ull / d); }
+MTSG_HD uint32_t mtsg_divmod(uint32_t n, uint32_t d, uint32_t rcp, uint32_t &rem) {
+    uint32_t q = (uint32_t)(((uint64_t)n * rcp) >> 32);
+    uint32_t r = n - q * d;
+    if (r >= d) { ++q; r -= d; }
+    rem = r;
+    return q;
+}
+
+// compact pixel index (8x8 tiles over the window's active rows, or the
+// window's every row_stride-th tile) -> image pixel; false: a padding pixel
+MTSG_HD bool pixel_of(const MtsgLaunch &L, uint32_t p, int &px, int &py) {
+    const uint32_t tile = p >> 6, in = p & 63;
+    if (L.tile_shard) {
+        const uint32_t t = tile * L.row_stride + L.row_phase;
+        uint32_t tx;
+        const uint32_t ty = mtsg_divmod(t, L.tiles_x, L.tiles_x_rcp, tx);
+        const uint32_t lx = tx * 8 + (in & 7), ly = ty * 8 + (in >> 3);
+        if (lx >= L.width || ly >= L.height) return false;
+        px = (int)(L.x0 + lx);
+        py = (int)(L.y0 + ly);
+        return true;
+    }
+    uint32_t tx;
+    const uint32_t ty = mtsg_divmod(tile, L.tiles_x, L.tiles_x_rcp, tx);
+    const uint32_t lx = tx * 8 + (in & 7);
+    const uint32_t r = ty * 8 + (in >> 3);
+    if (lx >= L.width) return false;
+    uint32_t off;
+    const uint32_t blk = mtsg_divmod(r, L.row_block, L.row_block_rcp, off);
+    const uint32_t ly = (blk * L.row_stride + L.row_phase) * L.row_block + off;
+    if (ly >= L.height) return false;
+    px = (int)(L.x0 + lx);
+    py = (int)(L.y0 + ly);
+    return true;
+}
+
+// The megakernel's sample runs (dmega.h): lane g renders runs q = g + k * lanes, k = 0, 1, ...;
+// run q is samples (q / num_pixels) * 2^s .. + 2^s - 1 of compact pixel q % num_pixels
+// (s = round_shift).  q only ever advances by `lanes`, so (q / P, q % P) is carried:
+// the lane's state is `round` = ((q / P) << s | sample within the run) of its NEXT item, plus
+// one run (the increment past a run's last sample carries into the run bits), and the
+// current run's pixel, which the path state holds anyway (PathState::pix).
+// mtsg_run_init leaves the state one run BEFORE the lane's first, so that the first
+// step advances like every other (wrapping 32-bit arithmetic; q / P < 2^(32 - s)).
+MTSG_HD void mtsg_launch_index(MtsgLaunch &L, uint64_t lanes) {   // host: the constants of a launch
+    L.tiles_x_rcp = mtsg_rcp32(L.tiles_x);
+    L.row_block_rcp = mtsg_rcp32(L.row_block);
+    L.run_dq = (uint32_t)(lanes / L.num_pixels);
+    L.run_dr = (uint32_t)(lanes % L.num_pixels);
+}
+MTSG_HD void mtsg_run_init(const MtsgLaunch &L, uint32_t g, uint32_t &round, uint32_t &pix) {
+    uint32_t jq = g / L.num_pixels, p = g % L.num_pixels;   // the one division per lane
+    if (p >= L.run_dr) p -= L.run_dr;
+    else { p += L.num_pixels - L.run_dr; --jq; }
+    jq -= L.run_dq;
+    round = (jq + 1u) << L.round_shift;
+    pix = p;
+}
+// the lane's next item: false when the lane has no more; else jj = the item's sample of the
+// chunk (jj >= chunk_spp: an odd tail's missing sample, nothing to render) at compact pixel pix
+MTSG_HD bool mtsg_run_step(const MtsgLaunch &L, uint32_t &round, uint32_t &pix, uint32_t &jj) {
+    const uint32_t rs = L.round_shift;
+    if ((round & ((1u << rs) - 1u)) == 0) {   // a new run: q += lanes
+        uint32_t jq = (round >> rs) - 1u + L.run_dq;
+        const uint32_t room = L.num_pixels - pix;
+        if (L.run_dr >= room) { pix = L.run_dr - room; ++jq; }
+        else pix += L.run_dr;
+        round = jq << rs;
+    }
+    if ((round >> rs) >= ((L.chunk_spp + ((1u << rs) - 1u)) >> rs)) return false;   // jq * 2^s >= chunk_spp
+    jj = round++;
+    return true;
+}
+
+// sobol::look_up (sobolseq.h:93-125) as the GF(2) solve it encodes: the index's high part is
+// jhi = Inv * ((sy ^ K) & mask), K the XOR of the second dimension's (top m bits of) columns
+// over the index bits.  Inv is linear, so the tables hold it already applied: tab[c][v],
+// c < 16, = Inv * (XOR of columns 4c .. 4c + 3 selected by v, & mask), and tab[16 + c][v],
+// c < 8, = Inv * ((v << 4c) & mask) for sy; jhi is the XOR of one word per nibble.
+#define MTSG_LUT_WORDS (16 * 16 + 8 * 16)
+MTSG_HD uint32_t mtsg_lut_fold(const MtsgLookup &Lu, uint32_t x) {
+    uint32_t r = 0;
+    for (uint32_t t = 0; t < Lu.m; ++t) r |= (uint32_t)(__builtin_popcount(Lu.inv[t] & x) & 1) << t;
+    return r;
+}
+MTSG_HD uint32_t mtsg_lut_word(const MtsgLookup &Lu, uint32_t i) {   // word i of the MTSG_LUT_WORDS
+    const uint32_t mask = Lu.m >= 32 ? 0xffffffffu : (1u << Lu.m) - 1u;
+    const uint32_t c = i >> 4, v = i & 15;
+    uint32_t x = 0;
+    if (c < 16) {
+        for (int b = 0; b < 4; ++b)
+            if ((v >> b) & 1) x ^= Lu.ycol[4 * c + b];
+    } else {
+        x = v << (4 * (c - 16));
+    }
+    return mtsg_lut_fold(Lu, x & mask);
+}
+template <int NIB, typename T>
+MTSG_HD uint32_t mtsg_lut_bits(T *tab, uint64_t index) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int c = 0; c < NIB; ++c) r ^= tab[c * 16 + (uint32_t)((index >> (4 * c)) & 15u)];
+    return r;
+}
+template <typename T>
+MTSG_HD uint64_t sobol_lookup_lds(const MtsgLookup &Lu, T *tab, uint32_t nibbles, uint32_t frame, uint32_t px,
+                                  uint32_t py, uint64_t scramble) {
+    const uint32_t m = Lu.m;
+    const uint32_t s = (uint32_t)((scramble & 0xFFFFFFFFull) >> (32 - m));
+    const uint32_t mask = (1u << m) - 1u;
+    const uint32_t sx = (px ^ s) & mask, sy = (py ^ s) & mask;
+    const uint32_t jlo = __builtin_bitreverse32(sx) >> (32 - m);
+    const uint64_t index = ((uint64_t)frame << (2 * m)) | jlo;
+    uint32_t jhi = (nibbles == 8) ? mtsg_lut_bits<8>(tab, index) : mtsg_lut_bits<MTSG_NIBBLES>(tab, index);
+    jhi ^= mtsg_lut_bits<4>(tab + 16 * 16, sy);
+    if (m > 16) jhi ^= mtsg_lut_bits<4>(tab + 20 * 16, sy >> 16);
+    return index | ((uint64_t)jhi << m);
+}
+

@@ -14,6 +14,9 @@
 #define PF_NAME2(a, N) a##N
 #define PF_NAME(a, N) PF_NAME2(a, N)
 
+// this object's view of the launch record (capi.cpp launch_layout_error)
+extern "C" uint32_t PF_NAME(mtsg_launch_bytes_path_f, PATH_FEAT)() { return (uint32_t)sizeof(MtsgLaunch); }
+
 namespace {
 constexpr int spec_feat(int bits) {
     return PATH_FEAT | (int)MTSG_FEAT_NOSTRICT | ((bits & 1) ? (int)MTSG_FEAT_GGX : 0) |

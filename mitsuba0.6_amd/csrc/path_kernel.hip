@@ -205,70 +205,16 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                    ANA = (FEAT & MTSG_FEAT_ANA) != 0;
     extern __shared__ uint32_t lds[];
     const MtsgDeviceScene &S = L.scene;
-    // LDS as path_kernel: [Sobol nibble tables][look_up column tables][scene (small scenes)][stacks]
-    const uint32_t tabWords = L.lds_dims * L.nibbles * 16;
-    for (uint32_t i = threadIdx.x; i < tabWords; i += BLOCK) {
-        const uint32_t d = i / (L.nibbles * 16), r = i % (L.nibbles * 16);
-        lds[i] = L.sobol_nib[(size_t)d * MTSG_NIBBLES * 16 + r];
-    }
-    for (uint32_t i = threadIdx.x; i < 16 * 16; i += BLOCK) {
-        const uint32_t c = i >> 4, v = i & 15;
-        uint32_t r = 0;
-        for (int b = 0; b < 4; ++b)
-            if ((v >> b) & 1) r ^= L.lut.ycol[4 * c + b];
-        lds[tabWords + i] = r;
-    }
-    const uint32_t base2 = tabWords + 16 * 16;
-    uint32_t sceneWords = 0;
-    if (SCENE_LDS) {
-        const uint32_t nodeWords = L.num_nodes * 16, triWords = S.num_prims * 12;
-        const uint32_t *gn = reinterpret_cast<const uint32_t *>(S.nodes);
-        const uint32_t *gt = reinterpret_cast<const uint32_t *>(S.tris);
-        for (uint32_t i = threadIdx.x; i < nodeWords; i += BLOCK) lds[base2 + i] = gn[i];
-        for (uint32_t i = threadIdx.x; i < triWords; i += BLOCK) lds[base2 + nodeWords + i] = gt[i];
-        sceneWords = nodeWords + triWords;
-        const uint32_t np = S.num_prims, nv = L.num_verts, ns = L.num_shapes * (sizeof(MtsgShape) / 4);
-        const uint32_t *srcs[5] = {S.prim_vtx, reinterpret_cast<const uint32_t *>(S.dpdu),
-                                   reinterpret_cast<const uint32_t *>(S.positions),
-                                   reinterpret_cast<const uint32_t *>(S.normals),
-                                   reinterpret_cast<const uint32_t *>(S.shapes)};
-        const uint32_t lens[5] = {4 * np, 3 * np, 3 * nv, 3 * nv, ns};
-        for (int a = 0; a < 5; ++a) {
-            for (uint32_t i = threadIdx.x; i < lens[a]; i += BLOCK) lds[base2 + sceneWords + i] = srcs[a][i];
-            sceneWords += lens[a];
-        }
-    }
-    __syncthreads();
-    lds_u32 *ycolTab = (lds_u32 *)(lds + tabWords);
-    lds_node *ldsNodes = (lds_node *)__builtin_assume_aligned((const void *)(lds + base2), 16);
-    lds_tri *ldsTris = (lds_tri *)__builtin_assume_aligned((const void *)(lds + base2 + L.num_nodes * 16), 16);
-    HitSrc<SCENE_LDS> hs;
-    if constexpr (SCENE_LDS) {
-        const uint32_t np = S.num_prims, nv = L.num_verts;
-        lds_u32 *b = (lds_u32 *)(lds + base2 + L.num_nodes * 16 + np * 12);
-        hs.pv = b;
-        hs.dpdu = (lds_f32 *)(b + 4 * np);
-        hs.pos = (lds_f32 *)(b + 7 * np);
-        hs.nrm = (lds_f32 *)(b + 7 * np + 3 * nv);
-        hs.shapes = (lds_shape *)(b + 7 * np + 6 * nv);
-    } else {
-        hs.pv = (glb_u32 *)S.prim_vtx;
-        hs.dpdu = (glb_f32 *)S.dpdu;
-        hs.pos = (glb_f32 *)S.positions;
-        hs.nrm = (glb_f32 *)S.normals;
-        hs.shapes = (glb_shape *)S.shapes;
-    }
-    SobolCtx SC;
-    SC.lds = (lds_u32 *)lds;
-    SC.glob = (glb_u32 *)L.sobol_nib;
-    SC.lds_dims = L.lds_dims;
-    SC.nibbles = L.nibbles;
-    SC.scramble = L.scramble;
-    SC.indep = L.sampler == MTSG_SAMPLER_INDEPENDENT;
-    SC.replay = false;   // the SFMT replay renders path / volpath only (capi.cpp)
-    SC.sfmt = nullptr;
-    lds_stk_n *stkN = (lds_stk_n *)(lds + base2 + sceneWords) + threadIdx.x;
-    lds_stk_d *stkD = (lds_stk_d *)(lds + base2 + sceneWords + L.stack_depth * BLOCK) + threadIdx.x;
+    // LDS as path_kernel: [Sobol nibble tables][look_up tables][scene (small scenes)][stacks]
+    const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
+    lds_u32 *ycolTab = V.ycolTab;
+    lds_node *ldsNodes = V.nodes;
+    lds_tri *ldsTris = V.tris;
+    const HitSrc<SCENE_LDS> &hs = V.hs;
+    // (the SFMT replay renders path / volpath only, capi.cpp: V.SC.replay is false here)
+    const SobolCtx &SC = V.SC;
+    lds_stk_n *stkN = (lds_stk_n *)(lds + V.stackBase) + threadIdx.x;
+    lds_stk_d *stkD = (lds_stk_d *)(lds + V.stackBase + L.stack_depth * BLOCK) + threadIdx.x;
     unsigned long long cRays = 0, cShadow = 0, cSamples = 0, cErr = 0, cN = 0, cT = 0;
 
     // closest hit / occlusion through the scene's structure (scan, LDS BVH or HBM BVH)
@@ -733,11 +679,14 @@ __global__ void arith_probe(const float *a, const float *b, float *out, int n) {
 // ---------------------------------------------------------------------------
 // host-side launchers (called by capi.cpp)
 // ---------------------------------------------------------------------------
+// this object's view of the launch record (capi.cpp launch_layout_error)
+extern "C" uint32_t mtsg_launch_bytes_path_kernel() { return (uint32_t)sizeof(MtsgLaunch); }
+
 size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
-    const size_t scene = L.scene_lds ? ((size_t)L.num_nodes * 16 + (size_t)L.scene.num_prims * (12 + 7) +
+    const size_t scene = L.scene_lds ? ((size_t)L.num_nodes * 16 + (size_t)L.scene.num_prims * (12 + 10) +
                                         (size_t)L.num_verts * 6 + (size_t)L.num_shapes * (sizeof(MtsgShape) / 4))
                                      : 0;
-    return ((size_t)L.lds_dims * L.nibbles * 16 + 16 * 16 + scene + ((size_t)L.stack_depth * 3 * BLOCK + 1) / 2) * 4;
+    return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS + scene + ((size_t)L.stack_depth * 3 * BLOCK + 1) / 2) * 4;
 }
 
 // the megakernel variants, one object per scene feature set (path_f.hip)

@@ -1082,10 +1082,33 @@ const std::vector<uint32_t> &mtsg_sobol_matrices() {
     return M;
 }
 
+// fill_hit's face normal (dpath.h; skdtree.h:355-360): cross(p1 - p0, p2 - p0) as dmath.h
+// forms it, its length by a correctly rounded sqrt, 1 / length, three products; left
+// as it is when it is all zero.  (This unit is built with -ffp-contract=off.)
+void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n) {
+    const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
+    const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
+    float x = (ay * bz) - (az * by), y = (az * bx) - (ax * bz), z = (ax * by) - (ay * bx);
+    const float length = std::sqrt(x * x + y * y + z * z);
+    if (!(x == 0 && y == 0 && z == 0)) {
+        const float r = 1.0f / length;
+        x *= r; y *= r; z *= r;
+    }
+    n[0] = x; n[1] = y; n[2] = z;
+}
+
 void mtsg_sobol_lookup_table(uint32_t m, MtsgLookup &L) {
     std::memset(&L, 0, sizeof L);
     L.m = m;
-    if (m <= 1 || m > 31) return;
+    if (m <= 1 || m > 31) return;   // (the kernels enumerate a 2 x 2 film's samples without look_up)
+    mtsg_sobol_lookup_solve(m, L);
+}
+
+// the GF(2) inverse for any 1 <= m <= 31 (mtsgpu_lookup_host checks m = 1 as well)
+void mtsg_sobol_lookup_solve(uint32_t m, MtsgLookup &L) {
+    std::memset(&L, 0, sizeof L);
+    L.m = m;
+    if (m < 1 || m > 31) return;
     const std::vector<uint32_t> &M = mtsg_sobol_matrices();
     for (int b = 0; b < 64; ++b) L.ycol[b] = b < MTSG_SOBOL_SIZE ? (M[MTSG_SOBOL_SIZE + b] >> (32 - m)) : 0u;
     uint32_t A[32], I[32];
@@ -1237,6 +1260,7 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
     S.normals.assign((size_t)verts * 3, 0.0f);
     S.prim_vtx.resize((size_t)prims * 4);
     S.dpdu.resize((size_t)prims * 3);
+    S.face_n.assign((size_t)prims * 3, 0.0f);
     S.shapes.resize(D->num_meshes);
     std::vector<BuildPrim> bp(prims);
     std::vector<MtsgTri> tacc(prims);
@@ -1401,6 +1425,8 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
             S.dpdu[3 * p] = dp.x; S.dpdu[3 * p + 1] = dp.y; S.dpdu[3 * p + 2] = dp.z;
             S.prim_vtx[4 * p] = voff + i0; S.prim_vtx[4 * p + 1] = voff + i1; S.prim_vtx[4 * p + 2] = voff + i2;
             S.prim_vtx[4 * p + 3] = si;
+            mtsg_face_normal(&S.positions[3 * (size_t)(voff + i0)], &S.positions[3 * (size_t)(voff + i1)],
+                             &S.positions[3 * (size_t)(voff + i2)], &S.face_n[3 * (size_t)p]);
             // TriAccel::load (triaccel.h:58-90)
             MtsgTri &ta = tacc[p];
             std::memset(&ta, 0, sizeof ta);

@@ -32,6 +32,7 @@ struct HostScene {
     std::vector<MtsgTri> tris;
     std::vector<uint32_t> prim_vtx;
     std::vector<float> dpdu, positions, normals;
+    std::vector<float> face_n;       // 3 per primitive: the unit face normal as fill_hit forms it (mtsg_face_normal)
     std::vector<MtsgShape> shapes;
     std::vector<MtsgBsdf> bsdfs;
     std::vector<MtsgEmitter> emitters;
@@ -54,10 +55,13 @@ struct HostScene {
 
 // Returns MTSGPU_OK or an error code; `err` receives the message.
 int mtsg_configure_scene(const mtsgpu_scene_desc *desc, HostScene &out, std::string &err);
+// the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dpath.h)
+void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n);
 void mtsg_build_qnodes(HostScene &S);   // host export only (mtsgpu_bvh_host)
 int mtsg_configure_filter(int32_t type, float param, MtsgFilter &f, std::string &err);
 // Sobol: 1024 x 52 matrices regenerated from the Joe-Kuo parameters, and the
 // look_up GF(2) tables for resolution 2^m.
 const std::vector<uint32_t> &mtsg_sobol_matrices();
 void mtsg_sobol_lookup_table(uint32_t m, MtsgLookup &lut);
+void mtsg_sobol_lookup_solve(uint32_t m, MtsgLookup &lut);
 uint64_t mtsg_sample_tea(uint32_t v0, uint32_t v1, int rounds);

@@ -22,7 +22,10 @@ __global__ void wf_flush(const unsigned long long *part, uint32_t blocks, unsign
 // ---------------------------------------------------------------------------
 // host-side launchers (capi.cpp)
 // ---------------------------------------------------------------------------
-size_t mtsg_wf_shade_lds_bytes(const MtsgLaunch &L) { return ((size_t)L.lds_dims * L.nibbles * 16 + 16 * 16) * 4; }
+// this object's view of the launch record (capi.cpp launch_layout_error)
+extern "C" uint32_t mtsg_launch_bytes_wf_kernel() { return (uint32_t)sizeof(MtsgLaunch); }
+
+size_t mtsg_wf_shade_lds_bytes(const MtsgLaunch &L) { return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS) * 4; }
 // The kd trace kernel: its mailbox in LDS at 8 waves/SIMD, the stack in scratch
 // (round 5, profiles/r05_ab_kd_mailbox_lds.log: C4 65.8 -> 76.9, C3 370 -> 398
 // Msamples/s; with the first 3 stack entries in LDS as well 75.1 / 371; the

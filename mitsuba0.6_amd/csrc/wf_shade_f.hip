@@ -5,4 +5,8 @@
 
 #define MTSG_WF_PICK_NAME2(N) mtsg_wf_pick_##N
 #define MTSG_WF_PICK_NAME(N) MTSG_WF_PICK_NAME2(N)
+#define MTSG_WF_BYTES_NAME2(N) mtsg_launch_bytes_wf_shade_f##N
+#define MTSG_WF_BYTES_NAME(N) MTSG_WF_BYTES_NAME2(N)
+// this object's view of the launch record (capi.cpp launch_layout_error)
+extern "C" uint32_t MTSG_WF_BYTES_NAME(WF_FEAT)() { return (uint32_t)sizeof(MtsgLaunch); }
 WfShadeFn MTSG_WF_PICK_NAME(WF_FEAT)(int wk, bool instr, bool ggx) { return wf_shade_pick_f<WF_FEAT>(wk, instr, ggx); }

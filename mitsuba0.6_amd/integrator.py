@@ -32,7 +32,8 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_group_render', 'mtsgpu_group_render_device', 'mtsgpu_group_member', 'mtsgpu_group_last_error',
            'mtsgpu_group_destroy', 'mtsgpu_trace_rays_ex', 'mtsgpu_debug_kdtree', 'mtsgpu_kdtree_host', 'mtsgpu_debug_libm',
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
-           'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host']
+           'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
+           'mtsgpu_face_normals_host']
 
 _lib = None
 
@@ -88,6 +89,11 @@ def load_library(path=None):
                                   P(C.c_uint32), C.c_size_t, P(C.c_uint32), C.c_char_p, C.c_size_t]
     if hasattr(L, 'mtsgpu_scan_host'):   # added within ABI 8: an A/B library of an earlier build has none
         L.mtsgpu_scan_host.argtypes = [P(abi.SceneDesc), P(C.c_float), C.c_size_t, P(C.c_uint32)]
+    if hasattr(L, 'mtsgpu_index_host'):   # added within ABI 8 as well
+        L.mtsgpu_index_host.argtypes = [P(C.c_uint32), P(C.c_uint32), C.c_size_t, P(C.c_uint32), P(C.c_uint32)]
+        L.mtsgpu_lookup_host.argtypes = [C.c_uint32, C.c_uint64, P(C.c_uint32), C.c_size_t, P(C.c_uint64)]
+    if hasattr(L, 'mtsgpu_face_normals_host'):
+        L.mtsgpu_face_normals_host.argtypes = [P(abi.SceneDesc), P(C.c_float), P(C.c_float), C.c_size_t, P(C.c_uint32)]
     L.mtsgpu_group_create.argtypes = [P(C.c_int), C.c_int, P(C.c_void_p)]
     L.mtsgpu_group_size.argtypes = [C.c_void_p]
     L.mtsgpu_group_upload_scene.argtypes = [C.c_void_p, P(abi.SceneDesc)]
@@ -156,6 +162,54 @@ def scan_host(scene):
     if rc != 0:
         raise MtsgpuError(rc, 'mtsgpu_scan_host')
     return rec, list(counts[:6]), list(counts[6:])
+
+
+def index_host(window, lane_round, row=(1, 1, 0), tile_shard=False, spp=1, run_shift=0, lanes=256):
+    """The megakernel's item -> pixel arithmetic on the host (mtsgpu_index_host), by the
+    functions the kernels compile: for each (lane, round) row of `lane_round` a row
+    (has_item, jj, pix, px, py, rendered) of uint32, and (compact pixels, tiles across).
+    window = (x0, y0, width, height); row = (block, stride, phase)."""
+    L = load_library()
+    geom = (C.c_uint32 * 11)(*window, *row, 1 if tile_shard else 0, spp, run_shift, lanes)
+    lr = np.ascontiguousarray(lane_round, np.uint32).reshape(-1, 2)
+    out = np.zeros((lr.shape[0], 6), np.uint32)
+    info = (C.c_uint32 * 2)()
+    up = C.POINTER(C.c_uint32)
+    rc = L.mtsgpu_index_host(geom, lr.ctypes.data_as(up), lr.shape[0], out.ctypes.data_as(up), info)
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_index_host')
+    return out, (int(info[0]), int(info[1]))
+
+
+def face_normals_host(scene):
+    """The per-primitive unit face normals staged with an LDS scene, formed on the host
+    without a device (mtsgpu_face_normals_host): (normals (N, 3), corners (N, 3, 3)) float32."""
+    L = load_library()
+    d = scene.desc()
+    n = C.c_uint32()
+    rc = L.mtsgpu_face_normals_host(C.byref(d), None, None, 0, C.byref(n))
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_face_normals_host')
+    nrm = np.zeros((n.value, 3), np.float32)
+    cor = np.zeros((n.value, 3, 3), np.float32)
+    fp = C.POINTER(C.c_float)
+    rc = L.mtsgpu_face_normals_host(C.byref(d), nrm.ctypes.data_as(fp), cor.ctypes.data_as(fp), n.value, C.byref(n))
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_face_normals_host')
+    return nrm, cor
+
+
+def lookup_host(m, scramble, px_py_j):
+    """sobol::look_up at film resolution 2^m through the kernels' folded tables
+    (mtsgpu_lookup_host): the uint64 sequence index of each (px, py, j) row."""
+    L = load_library()
+    q = np.ascontiguousarray(px_py_j, np.uint32).reshape(-1, 3)
+    out = np.zeros(q.shape[0], np.uint64)
+    rc = L.mtsgpu_lookup_host(m, scramble, q.ctypes.data_as(C.POINTER(C.c_uint32)), q.shape[0],
+                              out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc != 0:
+        raise MtsgpuError(rc, 'mtsgpu_lookup_host')
+    return out
 
 
 def kdtree_host(scene):
