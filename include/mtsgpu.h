@@ -370,6 +370,82 @@ int mtsgpu_develop_device(mtsgpu_ctx *ctx, const mtsgpu_develop_params *params, 
                           void *out_device, void *stream);
 /* Same from and to host memory (stages both through the context's buffers). */
 int mtsgpu_develop(mtsgpu_ctx *ctx, const mtsgpu_develop_params *params, const float *film, void *out);
+/* ---- field and multichannel integrators (AOV output) ----------------------
+ * FieldIntegrator (src/integrators/misc/field.cpp:55-187) extracts one field of
+ * the camera ray's intersection record per sample; MultiChannelIntegrator
+ * (src/integrators/misc/multichannel.cpp:87-262) runs several nested
+ * integrators per sample into one EMultiSpectrumAlphaWeight block, which
+ * hdrfilm stores and develops per pixel format (src/films/hdrfilm.cpp:215-292,
+ * 351-356, 488-494; Bitmap::convertMultiSpectrumAlphaWeight,
+ * src/libcore/bitmap.cpp:1595-1683).
+ * MTSGPU_FIELD_* = FieldIntegrator::EField (field.cpp:57-67). */
+enum { MTSGPU_FIELD_POSITION = 0,      /* its.p                                          */
+       MTSGPU_FIELD_REL_POSITION = 1,  /* world -> camera (the sensor transform's        */
+                                       /* inverse) applied to its.p                      */
+       MTSGPU_FIELD_DISTANCE = 2,      /* Spectrum(its.t)                                */
+       MTSGPU_FIELD_GEO_NORMAL = 3,    /* its.geoFrame.n                                 */
+       MTSGPU_FIELD_SH_NORMAL = 4,     /* its.shFrame.n                                  */
+       MTSGPU_FIELD_UV = 5,            /* (its.uv.x, its.uv.y, 0)                        */
+       MTSGPU_FIELD_ALBEDO = 6,        /* its.shape->getBSDF()->getDiffuseReflectance    */
+       MTSGPU_FIELD_SHAPE_INDEX = 7,   /* index of its.shape in the scene's shapes       */
+       MTSGPU_FIELD_PRIM_INDEX = 8,    /* its.primIndex (analytic shapes: KNoTriangleFlag) */
+       MTSGPU_FIELD_COUNT = 9 };
+#define MTSGPU_MAX_FIELDS 8
+typedef struct {                    /* one FieldIntegrator (field.cpp:69-110)       */
+    int32_t field;                  /* MTSGPU_FIELD_* ('field')                    */
+    float undefined[3];             /* 'undefined': the value where nothing is hit */
+} mtsgpu_field_desc;
+/* Render `num_fields` (1..MTSGPU_MAX_FIELDS) fields of the window in one pass: the
+ * primary ray of every sample is traced once, whatever the number of fields
+ * (multichannel.cpp:191-218: one rRec.rayIntersect, then every Li).  `films`
+ * receives num_fields consecutive films, each in the mtsgpu_render layout
+ * {f.r, f.g, f.b, alpha, w} and summed in the same fixed order, negative values
+ * kept (multichannel's blocks are built with warnInvalid off, multichannel.cpp:
+ * 143-145).  Alpha is always opacity: renderBlock never strips EOpacity
+ * (multichannel.cpp:181-215).  `samples` may be NULL; otherwise it receives one
+ * record per (pixel, sample) of the window, row-major pixel order, sample-minor,
+ * of 4 + 3*num_fields floats {samplePos.x, samplePos.y, alpha, hit, f0.rgb,
+ * f1.rgb, ...}.  `params` contributes spp, scramble, sampler, rfilter*, the
+ * window, the row / tile shard fields and cancel; its integrator fields are
+ * ignored.  The sample positions are those of a mtsgpu_render with the same
+ * params (the sampler's first 2D draw).  MTSGPU_EINVAL: num_fields of 0 or above
+ * MTSGPU_MAX_FIELDS, an unknown field, or an SFMT replay sampler (its draw
+ * positions depend on how many numbers the radiance integrator consumed, so a
+ * separate pass cannot reproduce the sample positions).  Blocking. */
+int mtsgpu_render_fields(mtsgpu_ctx *ctx, const mtsgpu_render_params *params, const mtsgpu_field_desc *fields,
+                         uint32_t num_fields, float *films, float *samples, mtsgpu_stats *stats);
+/* Same with `films_device` a device pointer to the num_fields films; `stream` a
+ * hipStream_t (NULL: the context's stream). */
+int mtsgpu_render_fields_device(mtsgpu_ctx *ctx, const mtsgpu_render_params *params, const mtsgpu_field_desc *fields,
+                                uint32_t num_fields, float *films_device, void *stream, mtsgpu_stats *stats);
+/* hdrfilm develop with several pixel formats (hdrfilm.cpp:488-494 ->
+ * Bitmap::convertMultiSpectrumAlphaWeight, bitmap.cpp:1608-1683): `films` is an
+ * array of num_films film pointers of one size, film i holding nested
+ * integrator i's {r, g, b, alpha, w}; film 0 also supplies alpha and weight.
+ * Per pixel: invWeight = w == 0 ? 0 : 1/w, alpha = a * invWeight, and film i's
+ * rgb times invWeight is converted by pixel_format[i] (bitmap.cpp:1617-1673;
+ * luminance and XYZ of the weighted value), then every channel by the component
+ * conversion of mtsgpu_develop (multiplier 1).  Output: the interior's pixels,
+ * channels interleaved in format order. */
+typedef struct {
+    uint32_t film_width, film_height;   /* each film incl. borders (W+2b, H+2b)         */
+    uint32_t border;                    /* b                                             */
+    uint32_t num_films;                 /* 1..MTSGPU_MAX_FIELDS + 1                      */
+    int32_t pixel_format[MTSGPU_MAX_FIELDS + 1];   /* MTSGPU_PIX_* per film             */
+    int32_t component_format;           /* MTSGPU_COMP_*                                 */
+} mtsgpu_develop_multi_params;
+/* Host memory (films and out; staged through the context's buffers). */
+int mtsgpu_develop_multi(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *params, const float *const *films,
+                         void *out);
+/* `films` is a host array of device pointers, `out_device` a device pointer. */
+int mtsgpu_develop_multi_device(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *params,
+                                const float *const *films, void *out_device, void *stream);
+/* Host-only (no device needed): configure `scene` and return per BSDF the scalar
+ * factor of its getDiffuseReflectance: plastic 1 - m_fdrExt (plastic.cpp:219-221),
+ * roughplastic with a constant alpha m_externalRoughTransmittance->evalDiffuse(alpha)
+ * (roughplastic.cpp:309-315), -1 for a textured alpha (evaluated per hit), 1 for
+ * diffuse, 0 for every other BSDF.  factors: num_bsdfs floats. */
+int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, char *msg, size_t cap);
 /* Batch ray queries on the uploaded scene, one GPU lane per ray:
  * Scene::rayIntersect (closest hit, shadow = 0) or the occlusion test
  * (shadow = 1) of ShapeKDTree::rayIntersect (src/librender/skdtree.cpp:
@@ -455,7 +531,8 @@ int mtsgpu_debug_libm(mtsgpu_ctx *ctx, int fn, const float *a, const float *b, f
    samples, Sobol HBM words, diagnostic section cycles 11-14), and in 15 the
    kernel that ran: the megakernel's feature set (MTSG_FEAT_* bits of
    csrc/layout.h, BSDF-set bits included) | waves/SIMD << 8 | scene in LDS << 12,
-   or 1 << 16 for the wavefront engine */
+   1 << 16 for the wavefront engine, or 1 << 17 | scene in LDS << 12 after a
+   field pass (mtsgpu_render_fields) */
 int mtsgpu_debug_counters(mtsgpu_ctx *ctx, uint64_t *out16);
 /* n nextULong draws of the device's SFMT19937 (the SFMT replay samplers' generator)
    from Random(seed), or from the clone-th Random(&master) clone of it */

@@ -26,6 +26,11 @@ SAMPLER_SOBOL, SAMPLER_INDEPENDENT, SAMPLER_SFMT_REPLAY, SAMPLER_SFMT_BLOCKS = 0
 SAMPLE_RECORD_FLOATS = 8
 PIX_LUMINANCE, PIX_LUMINANCE_ALPHA, PIX_RGB, PIX_RGBA, PIX_XYZ, PIX_XYZA = 0, 1, 2, 3, 4, 5
 COMP_FLOAT16, COMP_FLOAT32, COMP_UINT32 = 0, 1, 2
+# FieldIntegrator::EField (MTSGPU_FIELD_*)
+(FIELD_POSITION, FIELD_REL_POSITION, FIELD_DISTANCE, FIELD_GEO_NORMAL, FIELD_SH_NORMAL, FIELD_UV, FIELD_ALBEDO,
+ FIELD_SHAPE_INDEX, FIELD_PRIM_INDEX) = range(9)
+FIELD_COUNT = 9
+MAX_FIELDS = 8
 
 _f3 = C.c_float * 3
 _f16 = C.c_float * 16
@@ -99,6 +104,18 @@ FLAG_TILE_SHARD = 16                     # row_stride/row_phase interleave 8x8 t
 class DevelopParams(C.Structure):
     _fields_ = [('film_width', C.c_uint32), ('film_height', C.c_uint32), ('border', C.c_uint32),
                 ('pixel_format', C.c_int32), ('component_format', C.c_int32), ('multiplier', C.c_float)]
+
+
+class FieldDesc(C.Structure):
+    """mtsgpu_field_desc (include/mtsgpu.h)."""
+    _fields_ = [('field', C.c_int32), ('undefined', _f3)]
+
+
+class DevelopMultiParams(C.Structure):
+    """mtsgpu_develop_multi_params (include/mtsgpu.h)."""
+    _fields_ = [('film_width', C.c_uint32), ('film_height', C.c_uint32), ('border', C.c_uint32),
+                ('num_films', C.c_uint32), ('pixel_format', C.c_int32 * (MAX_FIELDS + 1)),
+                ('component_format', C.c_int32)]
 
 
 class Stats(C.Structure):

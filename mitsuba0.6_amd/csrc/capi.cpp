@@ -36,6 +36,11 @@ hipError_t mtsg_launch_trace_kd(const MtsgDeviceScene &S, const uint32_t *kdNode
                                 int numCUs, hipStream_t stream);
 int mtsg_path_kernel_occupancy(const MtsgLaunch &L, int *blocksPerCU);
 int mtsg_path_variant(const MtsgLaunch &L);
+// the field pass (field_kernel.hip) and the multi-format develop (film_kernel.hip)
+hipError_t mtsg_launch_field(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream);
+int mtsg_field_occupancy(const MtsgLaunch &L, int *bpc);
+hipError_t mtsg_launch_develop_multi(const mtsgpu_develop_multi_params &P, const float *const *films, void *out,
+                                     int num_cus, hipStream_t s);
 hipError_t mtsg_launch_wf_shade(const MtsgLaunch &L, const MtsgWave &W, unsigned long long *part, int grid, int wk,
                                 bool ggx, bool instr, hipStream_t s);
 hipError_t mtsg_launch_wf_trace(const MtsgLaunch &L, const MtsgWave &W, unsigned long long *part, int grid,
@@ -97,6 +102,8 @@ struct mtsgpu_ctx {
     DevBuf qrays, qhits;      // mtsgpu_trace_rays staging
     DevBuf film_own, film_spill, samples, counters, contrib;
     DevBuf dev_in, dev_out;   // staging of mtsgpu_develop (host film -> developed image)
+    DevBuf field_first;       // the field pass: first global primitive of each shape (MtsgFieldArgs::shape_first)
+    std::vector<uint32_t> field_first_host;   // kept alive for the async upload
     // wavefront pipeline: path slots, ray queues and results, counters
     DevBuf wf_state, wf_ray, wf_rslot, wf_cls, wf_cnt, wf_hit, wf_hitrec, wf_occl, wf_live, wf_ovf, wf_part, wf_kind;
     DevBuf rp_order, rp_start, rp_sfmt;   // SFMT replay: render order, unit starts, streams
@@ -116,6 +123,7 @@ struct mtsgpu_ctx {
 extern "C" {
 uint32_t mtsg_launch_bytes_path_kernel();
 uint32_t mtsg_launch_bytes_wf_kernel();
+uint32_t mtsg_launch_bytes_field_kernel();
 #define MTSG_BYTES_DECL(N) uint32_t mtsg_launch_bytes_path_f##N(); uint32_t mtsg_launch_bytes_wf_shade_f##N();
 MTSG_BYTES_DECL(0) MTSG_BYTES_DECL(1) MTSG_BYTES_DECL(2) MTSG_BYTES_DECL(3) MTSG_BYTES_DECL(6) MTSG_BYTES_DECL(7)
 #undef MTSG_BYTES_DECL
@@ -130,6 +138,7 @@ const std::string &launch_layout_error() {
         const uint32_t mine = (uint32_t)sizeof(MtsgLaunch);
         const struct { const char *name; uint32_t bytes; } objs[] = {
             {"path_kernel", mtsg_launch_bytes_path_kernel()}, {"wf_kernel", mtsg_launch_bytes_wf_kernel()},
+            {"field_kernel", mtsg_launch_bytes_field_kernel()},
 #define MTSG_BYTES_ROW(N) {"path_f" #N, mtsg_launch_bytes_path_f##N()}, {"wf_shade_f" #N, mtsg_launch_bytes_wf_shade_f##N()},
             MTSG_BYTES_ROW(0) MTSG_BYTES_ROW(1) MTSG_BYTES_ROW(2) MTSG_BYTES_ROW(3) MTSG_BYTES_ROW(6) MTSG_BYTES_ROW(7)
 #undef MTSG_BYTES_ROW
@@ -687,13 +696,18 @@ static void launch_geometry(MtsgLaunch &L, uint32_t x0, uint32_t y0, uint32_t wi
     mtsg_launch_index(L, 0);   // the reciprocals; the megakernel's grid is known per chunk (render_impl)
 }
 
+// FJ: the field pass (mtsgpu_render_fields) -- the same window, sampler, filter, sharding and
+// film machinery with field_kernel in place of the integrator's kernel; film_host / film_dev
+// then hold FJ->n consecutive films and samples_host records of 4 + 3 * FJ->n floats
+struct FieldJob { const mtsgpu_field_desc *fields; uint32_t n; };
 static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *film_host, float *film_dev,
-                       float *samples_host, hipStream_t stream, mtsgpu_stats *stats) {
+                       float *samples_host, hipStream_t stream, mtsgpu_stats *stats, const FieldJob *FJ = nullptr) {
     if (!ctx || !P) return MTSGPU_EINVAL;
     if (!ctx->have_scene) return fail(ctx, MTSGPU_ESTATE, "render called before a successful upload_scene");
     if (!launch_layout_error().empty()) return fail(ctx, MTSGPU_ESTATE, launch_layout_error());
     if (P->spp == 0) return fail(ctx, MTSGPU_EINVAL, "sampleCount must be positive");
-    const bool pathLike = P->integrator == MTSGPU_INTEGRATOR_PATH || P->integrator == MTSGPU_INTEGRATOR_VOLPATH;
+    const uint32_t nFilms = FJ ? FJ->n : 1u;   // (the integrator fields of P are ignored by the field pass)
+    const bool pathLike = !FJ && (P->integrator == MTSGPU_INTEGRATOR_PATH || P->integrator == MTSGPU_INTEGRATOR_VOLPATH);
     if (pathLike && P->rr_depth <= 0)
         return fail(ctx, MTSGPU_EINVAL, "'rrDepth' must be set to a value greater than zero!");
     if (pathLike && P->max_depth <= 0 && P->max_depth != -1)
@@ -731,7 +745,7 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     L.rr_depth = P->rr_depth;
     L.strict_normals = P->strict_normals;
     L.hide_emitters = P->hide_emitters;
-    L.has_alpha = P->has_alpha;
+    L.has_alpha = FJ ? 1 : P->has_alpha;
     L.film_w = (int)H.film_w;
     L.film_h = (int)H.film_h;
     L.fw = (int)H.film_w + 2 * L.filter.border;
@@ -742,13 +756,16 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     L.face_n = (const float *)ctx->face_n.p;
     // Sobol index width: frame << 2m | 2m bits (sobolseq.h:93-125); 52 columns per dimension
     // the direct integrator's 2D sample arrays index the Sobol sequence at spp x count
-    const bool direct = P->integrator == MTSGPU_INTEGRATOR_DIRECT;
-    if (!pathLike && !direct) return fail(ctx, MTSGPU_EINVAL, "unknown integrator");
+    const bool direct = !FJ && P->integrator == MTSGPU_INTEGRATOR_DIRECT;
+    if (!pathLike && !direct && !FJ) return fail(ctx, MTSGPU_EINVAL, "unknown integrator");
     if (direct && P->emitter_samples + P->bsdf_samples == 0)
         return fail(ctx, MTSGPU_EINVAL, "direct: emitterSamples + bsdfSamples must be positive");
     if (P->sampler < MTSGPU_SAMPLER_SOBOL || P->sampler > MTSGPU_SAMPLER_SFMT_BLOCKS)
         return fail(ctx, MTSGPU_EINVAL, "unknown sampler");
     const bool replay = P->sampler == MTSGPU_SAMPLER_SFMT_REPLAY || P->sampler == MTSGPU_SAMPLER_SFMT_BLOCKS;
+    if (replay && FJ)
+        return fail(ctx, MTSGPU_EINVAL, "field pass: the SFMT replay samplers' draw positions depend on how many numbers the "
+                                        "radiance integrator consumed; a separate pass cannot reproduce the sample positions");
     if (replay && (!pathLike || L.row_stride > 1 || P->width > 65535 || P->height > 65535))
         return fail(ctx, MTSGPU_EINVAL, "SFMT replay: path/volpath over a whole crop window (no row shards)");
     L.sampler = (uint32_t)P->sampler;
@@ -814,7 +831,7 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
         if (L.bset && envOnly) L.bset |= (uint32_t)MTSG_FEAT_NOREFN;
     }
     // MIDirectIntegrator::configure / configureSampler (direct.cpp:128-143)
-    L.integrator = P->integrator;
+    L.integrator = FJ ? (int32_t)MTSGPU_INTEGRATOR_PATH : P->integrator;
     L.array_end = 5;
     if (direct) {
         const uint32_t nl = P->emitter_samples, nb = P->bsdf_samples;
@@ -871,19 +888,23 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     }
     if (const char *env = std::getenv("MTSGPU_CONTRIB_BYTES")) budget = std::max<size_t>(std::strtoull(env, nullptr, 10), 1 << 20);
     const size_t perSample = (size_t)L.num_pixels * (L.gather ? 32 : 16);   // one (gather mode: two) float4 per sample
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(P->spp, budget / perSample));
+    // (the field pass keeps one record array per field under the same budget)
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(P->spp, budget / (perSample * nFilms)));
     const size_t filmFloats = (size_t)L.fw * L.fh * 5;
-    if ((e = ctx->film_own.ensure(filmFloats * 4)) != hipSuccess || (e = ctx->film_spill.ensure(filmFloats * 8)) != hipSuccess ||
-        (e = ctx->counters.ensure(16 * 8)) != hipSuccess || (e = ctx->contrib.ensure(perSample * (chunk + (chunk & 1)))) != hipSuccess)
+    const size_t fieldBytes = perSample * (chunk + (chunk & 1));   // one field's record array
+    if ((e = ctx->film_own.ensure(filmFloats * 4 * nFilms)) != hipSuccess ||
+        (e = ctx->film_spill.ensure(filmFloats * 8 * nFilms)) != hipSuccess ||
+        (e = ctx->counters.ensure(16 * 8)) != hipSuccess || (e = ctx->contrib.ensure(fieldBytes * nFilms)) != hipSuccess)
         return hip_fail(ctx, e, "film allocation");
     float *own = film_dev ? film_dev : (float *)ctx->film_own.p;
-    const size_t nsamp = samples_host ? (size_t)P->width * P->height * P->spp * MTSGPU_SAMPLE_RECORD_FLOATS : 0;
+    const size_t recFloats = FJ ? 4 + 3 * (size_t)nFilms : (size_t)MTSGPU_SAMPLE_RECORD_FLOATS;
+    const size_t nsamp = samples_host ? (size_t)P->width * P->height * P->spp * recFloats : 0;
     if (nsamp) {
         if ((e = ctx->samples.ensure(nsamp * 4)) != hipSuccess) return hip_fail(ctx, e, "sample buffer");
         if ((e = hipMemsetAsync(ctx->samples.p, 0, nsamp * 4, stream)) != hipSuccess) return hip_fail(ctx, e, "memset");
     }
-    if ((e = hipMemsetAsync(own, 0, filmFloats * 4, stream)) != hipSuccess ||
-        (e = hipMemsetAsync(ctx->film_spill.p, 0, filmFloats * 8, stream)) != hipSuccess ||
+    if ((e = hipMemsetAsync(own, 0, filmFloats * 4 * nFilms, stream)) != hipSuccess ||
+        (e = hipMemsetAsync(ctx->film_spill.p, 0, filmFloats * 8 * nFilms, stream)) != hipSuccess ||
         (e = hipMemsetAsync(ctx->counters.p, 0, 16 * 8, stream)) != hipSuccess)
         return hip_fail(ctx, e, "memset");
     L.film_own = own;
@@ -893,8 +914,29 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     unsigned long long *cnt = (unsigned long long *)ctx->counters.p;
     L.counters = cnt;
 
+    MtsgFieldArgs FA;
+    std::memset(&FA, 0, sizeof FA);
+    if (FJ) {
+        FA.num_fields = nFilms;
+        FA.record_floats = (uint32_t)recFloats;
+        FA.contrib_stride = fieldBytes / 4;
+        for (uint32_t f = 0; f < nFilms; ++f) {
+            FA.field[f] = FJ->fields[f].field;
+            for (int k = 0; k < 3; ++k) FA.undefined[f][k] = FJ->fields[f].undefined[k];
+            FA.spill[f] = L.film_spill + f * filmFloats;
+        }
+        // sensor->getWorldTransform()->eval(its.t).inverse() (field.cpp:137-139)
+        if (!mtsg_invert4(H.cam.to_world, FA.world_to_cam)) return fail(ctx, MTSGPU_EINVAL, "Singular matrix in Matrix::invert");
+        // its.primIndex counts within the mesh: the first global primitive of each shape
+        std::vector<uint32_t> &first = ctx->field_first_host;
+        first.assign(H.shapes.size(), 0u);
+        for (size_t p = H.prim_vtx.size() / 4; p-- > 0;) first[H.prim_vtx[4 * p + 3]] = (uint32_t)p;
+        if ((e = upload(ctx->field_first, first, stream)) != hipSuccess) return hip_fail(ctx, e, "field upload");
+        FA.shape_first = (const uint32_t *)ctx->field_first.p;
+    }
     int bpc = 0;
-    mtsg_path_kernel_occupancy(L, &bpc);
+    if (FJ) mtsg_field_occupancy(L, &bpc);
+    else mtsg_path_kernel_occupancy(L, &bpc);
     if (bpc <= 0) bpc = 1;
     const bool stats_mode = (P->flags & MTSGPU_FLAG_TRAVERSAL_STATS) != 0;
     if (replay) {
@@ -926,7 +968,8 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     if (P->flags & MTSGPU_FLAG_WAVEFRONT) wave = pathLike;
     if (P->flags & MTSGPU_FLAG_MEGAKERNEL) wave = false;
     if (replay) wave = false;   // one lane per replay unit
-    if (P->flags & MTSGPU_FLAG_KDTREE) {
+    if (FJ) wave = false;
+    if (!FJ && (P->flags & MTSGPU_FLAG_KDTREE)) {
         // the reference's own kd-tree: the wavefront engine with wf_trace_kd
         if (!pathLike || replay)
             return fail(ctx, MTSGPU_EINVAL, "kd-tree traversal: path / volpath with the sobol or independent sampler");
@@ -1004,16 +1047,26 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
                 return fail(ctx, MTSGPU_EINVAL, "SFMT replay: more 32x32 blocks than resident lanes (crop too large)");
             L.round_shift = run_shift(L, (uint64_t)grid * BLOCK_THREADS);
             mtsg_launch_index(L, (uint64_t)grid * BLOCK_THREADS);
-            if ((e = mtsg_launch_path(L, grid, nsamp != 0, stats_mode, stream)) != hipSuccess) return hip_fail(ctx, e, "path kernel launch");
+            if (FJ) {
+                if ((e = mtsg_launch_field(L, FA, grid, stream)) != hipSuccess) return hip_fail(ctx, e, "field kernel launch");
+            } else if ((e = mtsg_launch_path(L, grid, nsamp != 0, stats_mode, stream)) != hipSuccess) {
+                return hip_fail(ctx, e, "path kernel launch");
+            }
         }
-        if ((e = L.gather ? mtsg_launch_gather(L, stream) : mtsg_launch_reduce(L, stream)) != hipSuccess)
-            return hip_fail(ctx, e, "film reduce launch");
+        // (the field pass: every field's record array into its own film, by the same kernels)
+        for (uint32_t f = 0; f < nFilms; ++f) {
+            MtsgLaunch Lf = L;
+            Lf.contrib = L.contrib + f * (fieldBytes / 4);
+            Lf.film_own = own + f * filmFloats;
+            if ((e = Lf.gather ? mtsg_launch_gather(Lf, stream) : mtsg_launch_reduce(Lf, stream)) != hipSuccess)
+                return hip_fail(ctx, e, "film reduce launch");
+        }
     }
     if ((e = hipEventRecord(ctx->ev1, stream)) != hipSuccess) return hip_fail(ctx, e, "event");
-    if ((e = mtsg_launch_finalize(own, L.film_spill, filmFloats, stream)) != hipSuccess) return hip_fail(ctx, e, "finalize launch");
+    if ((e = mtsg_launch_finalize(own, L.film_spill, filmFloats * nFilms, stream)) != hipSuccess) return hip_fail(ctx, e, "finalize launch");
     unsigned long long hc[16];
     if ((e = hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, stream)) != hipSuccess) return hip_fail(ctx, e, "counters");
-    if (film_host && (e = hipMemcpyAsync(film_host, own, filmFloats * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+    if (film_host && (e = hipMemcpyAsync(film_host, own, filmFloats * 4 * nFilms, hipMemcpyDeviceToHost, stream)) != hipSuccess)
         return hip_fail(ctx, e, "film copy");
     if (nsamp && (e = hipMemcpyAsync(samples_host, ctx->samples.p, nsamp * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
         return hip_fail(ctx, e, "sample copy");
@@ -1025,6 +1078,8 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
     // (tests and A/B logs read it)
     if (wave) {
         ctx->last_counters[15] = 1ull << 16;
+    } else if (FJ) {   // field_kernel<SCENE_LDS, ..>: 1 << 17 | SCENE_LDS << 12
+        ctx->last_counters[15] = (1ull << 17) | ((unsigned long long)L.scene_lds << 12);
     } else {
         const int v = mtsg_path_variant(L);
         ctx->last_counters[15] = (unsigned long long)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) |
@@ -1061,6 +1116,38 @@ int mtsgpu_render_device(mtsgpu_ctx *ctx, const mtsgpu_render_params *params, fl
                          mtsgpu_stats *stats) {
     if (!film_device) return fail(ctx, MTSGPU_EINVAL, "film buffer is NULL");
     return render_impl(ctx, params, nullptr, film_device, nullptr, (hipStream_t)stream, stats);
+}
+
+namespace {
+int field_job_check(mtsgpu_ctx *ctx, const mtsgpu_field_desc *fields, uint32_t n) {
+    if (!ctx) return MTSGPU_EINVAL;
+    if (!fields) return fail(ctx, MTSGPU_EINVAL, "field list is NULL");
+    if (n == 0) return fail(ctx, MTSGPU_EINVAL, "No sub-integrators were supplied to the multi-channel integrator!");
+    if (n > MTSGPU_MAX_FIELDS) return fail(ctx, MTSGPU_EINVAL, "at most 8 fields per pass");
+    for (uint32_t f = 0; f < n; ++f)
+        if (fields[f].field < 0 || fields[f].field >= MTSGPU_FIELD_COUNT)
+            return fail(ctx, MTSGPU_EINVAL, "Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', "
+                                            "'geoNormal', 'shNormal', 'primIndex', 'shapeIndex', or 'uv'!");
+    return MTSGPU_OK;
+}
+}  // namespace
+
+int mtsgpu_render_fields(mtsgpu_ctx *ctx, const mtsgpu_render_params *params, const mtsgpu_field_desc *fields,
+                         uint32_t num_fields, float *films, float *samples, mtsgpu_stats *stats) {
+    const int rc = field_job_check(ctx, fields, num_fields);
+    if (rc != MTSGPU_OK) return rc;
+    if (!films) return fail(ctx, MTSGPU_EINVAL, "film buffer is NULL");
+    const FieldJob job = {fields, num_fields};
+    return render_impl(ctx, params, films, nullptr, samples, nullptr, stats, &job);
+}
+
+int mtsgpu_render_fields_device(mtsgpu_ctx *ctx, const mtsgpu_render_params *params, const mtsgpu_field_desc *fields,
+                                uint32_t num_fields, float *films_device, void *stream, mtsgpu_stats *stats) {
+    const int rc = field_job_check(ctx, fields, num_fields);
+    if (rc != MTSGPU_OK) return rc;
+    if (!films_device) return fail(ctx, MTSGPU_EINVAL, "film buffer is NULL");
+    const FieldJob job = {fields, num_fields};
+    return render_impl(ctx, params, nullptr, films_device, nullptr, (hipStream_t)stream, stats, &job);
 }
 
 // hdrfilm develop (film_kernel.hip)
@@ -1112,6 +1199,83 @@ int mtsgpu_develop(mtsgpu_ctx *ctx, const mtsgpu_develop_params *P, const float 
     return MTSGPU_OK;
 }
 
+namespace {
+int develop_multi_check(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *P, const float *const *films, size_t *out_bytes) {
+    if (!ctx) return MTSGPU_EINVAL;
+    if (!P || !films) return fail(ctx, MTSGPU_EINVAL, "develop: NULL argument");
+    if (P->num_films == 0 || P->num_films > MTSGPU_MAX_FIELDS + 1) return fail(ctx, MTSGPU_EINVAL, "develop: bad film count");
+    size_t ch = 0;
+    for (uint32_t f = 0; f < P->num_films; ++f) {
+        const int c = mtsg_develop_channels(P->pixel_format[f]);
+        if (!c) return fail(ctx, MTSGPU_EINVAL, "develop: unknown pixel format");
+        if (!films[f]) return fail(ctx, MTSGPU_EINVAL, "develop: NULL buffer");
+        ch += (size_t)c;
+    }
+    if (P->component_format < MTSGPU_COMP_FLOAT16 || P->component_format > MTSGPU_COMP_UINT32)
+        return fail(ctx, MTSGPU_EINVAL, "develop: unknown component format");
+    if (P->film_width <= 2 * P->border || P->film_height <= 2 * P->border)
+        return fail(ctx, MTSGPU_EINVAL, "develop: film smaller than its borders");
+    const size_t n = (size_t)(P->film_width - 2 * P->border) * (P->film_height - 2 * P->border);
+    *out_bytes = n * ch * (P->component_format == MTSGPU_COMP_FLOAT16 ? 2 : 4);
+    return MTSGPU_OK;
+}
+}  // namespace
+
+int mtsgpu_develop_multi_device(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *P, const float *const *films,
+                                void *out_device, void *stream) {
+    size_t ob = 0;
+    const int rc = develop_multi_check(ctx, P, films, &ob);
+    if (rc != MTSGPU_OK) return rc;
+    if (!out_device) return fail(ctx, MTSGPU_EINVAL, "develop: NULL buffer");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipError_t e = mtsg_launch_develop_multi(*P, films, out_device, ctx->num_cus, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e == hipSuccess ? MTSGPU_OK : hip_fail(ctx, e, "develop");
+}
+
+int mtsgpu_develop_multi(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *P, const float *const *films, void *out) {
+    size_t ob = 0;
+    const int rc = develop_multi_check(ctx, P, films, &ob);
+    if (rc != MTSGPU_OK) return rc;
+    if (!out) return fail(ctx, MTSGPU_EINVAL, "develop: NULL buffer");
+    (void)hipSetDevice(ctx->device);
+    const size_t ib = (size_t)P->film_width * P->film_height * 5 * sizeof(float);
+    hipError_t e;
+    if ((e = ctx->dev_in.ensure(ib * P->num_films)) != hipSuccess || (e = ctx->dev_out.ensure(ob)) != hipSuccess)
+        return hip_fail(ctx, e, "develop buffers");
+    hipStream_t s = ctx->stream;
+    const float *dev[MTSGPU_MAX_FIELDS + 1] = {};
+    for (uint32_t f = 0; f < P->num_films; ++f) {
+        dev[f] = (const float *)((const char *)ctx->dev_in.p + f * ib);
+        if ((e = hipMemcpyAsync((void *)dev[f], films[f], ib, hipMemcpyHostToDevice, s)) != hipSuccess)
+            return hip_fail(ctx, e, "develop");
+    }
+    if ((e = mtsg_launch_develop_multi(*P, dev, ctx->dev_out.p, ctx->num_cus, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(out, ctx->dev_out.p, ob, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(ctx, e, "develop");
+    return MTSGPU_OK;
+}
+
+int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, char *msg, size_t cap) {
+    if (!scene || !factors) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    const int rc = mtsg_configure_scene(scene, H, err);
+    if (rc != MTSGPU_OK) {
+        if (msg && cap) std::snprintf(msg, cap, "%s", err.c_str());
+        return rc;
+    }
+    for (uint32_t i = 0; i < scene->num_bsdfs; ++i) {
+        const MtsgBsdf &b = H.bsdfs[i];
+        factors[i] = b.type == MTSGPU_BSDF_DIFFUSE ? 1.0f
+                   : b.type == MTSGPU_BSDF_PLASTIC ? 1 - b.fdr_ext
+                   : b.type == MTSGPU_BSDF_ROUGHPLASTIC ? (b.alpha_tex.type ? -1.0f : b.ftr_ext) : 0.0f;
+    }
+    return MTSGPU_OK;
+}
+
 const char *mtsgpu_last_error(mtsgpu_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 void mtsgpu_destroy(mtsgpu_ctx *ctx) {
@@ -1121,7 +1285,7 @@ void mtsgpu_destroy(mtsgpu_ctx *ctx) {
                       &ctx->shapes, &ctx->bsdfs, &ctx->emitters, &ctx->area_cdf, &ctx->em_cdf, &ctx->sobol,
                       &ctx->film_own, &ctx->film_spill, &ctx->samples, &ctx->counters, &ctx->contrib,
                       &ctx->env, &ctx->env_texels, &ctx->env_rows, &ctx->env_cols, &ctx->env_weights, &ctx->env_grows, &ctx->env_gcols,
-                      &ctx->rtrans, &ctx->texcoords, &ctx->qrays, &ctx->qhits,
+                      &ctx->rtrans, &ctx->texcoords, &ctx->qrays, &ctx->qhits, &ctx->field_first,
                       &ctx->dev_in, &ctx->dev_out, &ctx->wf_state, &ctx->wf_ray, &ctx->wf_rslot, &ctx->wf_cls,
                       &ctx->wf_cnt, &ctx->wf_hit, &ctx->wf_hitrec, &ctx->wf_occl, &ctx->wf_live, &ctx->wf_ovf, &ctx->wf_part, &ctx->wf_kind, &ctx->rp_order, &ctx->rp_start, &ctx->rp_sfmt, &ctx->env_grows, &ctx->env_gcols};
     for (DevBuf *b : bufs) b->release();

@@ -917,11 +917,17 @@ __device__ __forceinline__ float filter_disc(const MtsgFilter &F, float x) {
     return F.values[i];
 }
 
+// WARN = false: an ImageBlock built with warnInvalid off (the multichannel integrator's,
+// multichannel.cpp:143-145) takes negative and non-finite values as they are.
+// spill: the neighbour-splat film, L.film_spill unless given (the field pass has one per field)
+template <bool WARN = true>
 __device__ __forceinline__ bool film_splat(const MtsgLaunch &L, int px, int py, float sx, float sy,
-                                           const float *val, float &ownW) {
+                                           const float *val, float &ownW, double *spill = nullptr) {
+    if constexpr (WARN) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i)
-        if (!isfinite(val[i]) || val[i] < 0) return false;
+        for (int i = 0; i < 5; ++i)
+            if (!isfinite(val[i]) || val[i] < 0) return false;
+    }
     const MtsgFilter &F = L.filter;
     const int b = F.border;
     const int bx = (px / MTSG_BLOCK_SIZE) * MTSG_BLOCK_SIZE, by = (py / MTSG_BLOCK_SIZE) * MTSG_BLOCK_SIZE;
@@ -945,7 +951,7 @@ __device__ __forceinline__ bool film_splat(const MtsgLaunch &L, int px, int py, 
                 // weight * value[k] in float as the reference forms it, summed in double:
                 // exact for contributions within 2^29 of each other, so the spill film
                 // does not depend on the order the atomics land (film_finalize rounds once)
-                double *dst = L.film_spill + ((size_t)gy * L.fw + gx) * 5;
+                double *dst = (spill ? spill : L.film_spill) + ((size_t)gy * L.fw + gx) * 5;
 #pragma unroll
                 for (int k = 0; k < 5; ++k) atomicAdd(dst + k, (double)(weight * val[k]));
             }
@@ -975,14 +981,17 @@ __device__ __forceinline__ size_t film_slot(const MtsgLaunch &L, uint32_t jj, ui
     return (size_t)jj * L.num_pixels + pix;
 }
 
+template <bool WARN = true>
 __device__ __forceinline__ void film_record(const MtsgLaunch &L, size_t slot, int px, int py, float sx, float sy,
-                                            const float *val, bool alpha) {
+                                            const float *val, bool alpha, double *spill = nullptr) {
     float4 rec4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (L.gather) {
         bool valid = true;
+        if constexpr (WARN) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (!isfinite(val[i]) || val[i] < 0) valid = false;   // (alpha and 1 are valid)
+            for (int i = 0; i < 3; ++i)
+                if (!isfinite(val[i]) || val[i] < 0) valid = false;   // (alpha and 1 are valid)
+        }
         if (valid) rec4 = make_float4(val[0], val[1], val[2], alpha ? sx : -sx);
         float4 *r = reinterpret_cast<float4 *>(L.contrib) + 2 * slot;
         r[0] = rec4;
@@ -990,7 +999,7 @@ __device__ __forceinline__ void film_record(const MtsgLaunch &L, size_t slot, in
         return;
     }
     float ownW = 0.0f;
-    if (film_splat(L, px, py, sx, sy, val, ownW)) rec4 = make_float4(val[0], val[1], val[2], alpha ? ownW : -ownW);
+    if (film_splat<WARN>(L, px, py, sx, sy, val, ownW, spill)) rec4 = make_float4(val[0], val[1], val[2], alpha ? ownW : -ownW);
     reinterpret_cast<float4 *>(L.contrib)[slot] = rec4;
 }
 

@@ -1,0 +1,183 @@
+// field_kernel.hip -- the `field` integrator (integrators/misc/field.cpp:55-187) as the
+// multichannel integrator runs it (integrators/misc/multichannel.cpp:164-221): one lane per
+// (pixel, sample) item; per item the sampler's first 2D draw, the camera ray, ONE closest-hit
+// query through the scene's own structure (tiny-scene scan, LDS BVH or HBM BVH; analytic
+// shapes included) and the intersection record with its uv -- then every requested field is
+// read off that one record.  The prologue is direct_kernel's (path_kernel.hip), so a field
+// sample sits at the position, and sees the hit, of the colour render's sample.
+//
+// Each field is recorded as {f.r, f.g, f.b, alpha, 1} through film_record (dpath.h) into its
+// own record array and summed by film_reduce / film_gather into its own ordinary 5-float
+// film.  multichannel's blocks are built with warnInvalid off (multichannel.cpp:143-145):
+// negative values (normals, positions) are kept, film_record<false>.
+//
+// Built with path_kernel.hip's flags (Makefile PK_FLAGS): it inlines the same traversal.
+#include "dpath.h"
+
+// PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298), as path_kernel.hip's
+__device__ __forceinline__ void field_camera_ray(const MtsgCamera &cam, float sx, float sy, f3 &ro, f3 &rd,
+                                                 float &mint, float &maxt) {
+    const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
+    const f3 dl = normalize(nearP);
+    const float invZ = 1.0f / dl.z;
+    mint = cam.near_clip * invZ;
+    maxt = cam.far_clip * invZ;
+    const float *W = cam.to_world;
+    ro = mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
+            W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);
+    rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
+            W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
+}
+
+// BSDF::getDiffuseReflectance(its) of the hit shape's BSDF
+__device__ __forceinline__ f3 field_albedo(const MtsgDeviceScene &S, GBsdf &top, const Hit &h) {
+    constexpr int BS = (int)MTSG_FEAT_EXT;
+    GBsdf *b = &top;
+    if (b->type == BSDF_TWOSIDED)   // twosided.cpp:198-203: its is handed on as it is
+        b = &((GBsdf *)S.bsdfs)[top.nested[h.wi.z > 0 ? 0 : 1]];
+    switch (b->type) {
+        case BSDF_DIFFUSE:   // diffuse.cpp:106-108
+            return bsdf_refl<BS>(*b, h.u, h.v);
+        case BSDF_PLASTIC:   // plastic.cpp:219-221
+            return mul(bsdf_refl<BS>(*b, h.u, h.v), 1 - b->fdr_ext);
+        case BSDF_ROUGHPLASTIC: {   // roughplastic.cpp:309-315
+            float ftr = b->ftr_ext;
+            if (b->alpha_tex.type) {   // RoughTransmittance::evalDiffuse, eta fixed (rtrans.h:254-259, 283)
+                const float alpha = avg3(tex_eval(b->alpha_tex, h.u, h.v));
+                const float r = cubic1d(rt_warp_alpha(*b, alpha), (glb_f32 *)S.rtrans + b->rt_int + b->rt_alpha,
+                                        (uint32_t)b->rt_alpha);
+                ftr = smin(1.0f, smax(0.0f, r));
+            }
+            return mul(bsdf_refl<BS>(*b, h.u, h.v), ftr);
+        }
+        default:   // BSDF::getDiffuseReflectance (bsdf.cpp:82-86): eval with typeMask = EDiffuseReflection,
+            return mk(0, 0, 0);   // which the conductors and dielectrics reject
+    }
+}
+
+template <bool SCENE_LDS, int FEAT>
+__global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLaunch L, MtsgFieldArgs FA) {
+    constexpr bool ANA = (FEAT & MTSG_FEAT_ANA) != 0;
+    extern __shared__ uint32_t lds[];
+    const MtsgDeviceScene &S = L.scene;
+    const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
+    lds_u32 *ycolTab = V.ycolTab;
+    lds_node *ldsNodes = V.nodes;
+    lds_tri *ldsTris = V.tris;
+    const HitSrc<SCENE_LDS> &hs = V.hs;
+    const SobolCtx &SC = V.SC;   // (no SFMT replay: capi.cpp refuses it)
+    lds_stk_n *stkN = (lds_stk_n *)(lds + V.stackBase) + threadIdx.x;
+    lds_stk_d *stkD = (lds_stk_d *)(lds + V.stackBase + L.stack_depth * BLOCK) + threadIdx.x;
+    unsigned long long cSamples = 0, cErr = 0, cN = 0, cT = 0;
+
+    const uint64_t lanes = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t it = (uint64_t)xcd_block(L.xcds) * BLOCK + threadIdx.x; it < L.num_items; it += lanes) {
+        const uint32_t jj = (uint32_t)(it / L.num_pixels);
+        const uint32_t pix = (uint32_t)(it - (uint64_t)jj * L.num_pixels);
+        int px, py;
+        if (!pixel_of(L, pix, px, py)) continue;
+        const uint32_t j = L.j0 + jj;
+        SamplerState smp;
+        smp.dim = 0;
+        smp.sampleIndex = j;
+        smp.err = false;
+        smp.sobolIndex = SC.indep ? indep_key((uint32_t)px, (uint32_t)py, j)
+                       : (L.lut.m > 1) ? sobol_lookup_lds(L.lut, ycolTab, L.nibbles, j, (uint32_t)px, (uint32_t)py,
+                                                          L.scramble64)
+                                       : (uint64_t)j;
+        float u, v;
+        next2d(SC, L.resolution, smp, px, py, u, v);
+        const float sx = (float)px + u, sy = (float)py + v;
+        f3 ro, rd;
+        float rmint, rmaxt;
+        field_camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
+
+        // rRec.rayIntersect(sensorRay): the one closest-hit query of the sample
+        float mint, maxt;
+        uint32_t slot = 0, prim = 0;
+        float hu = 0, hv = 0, ht = 0;
+        bool hit = false;
+        if (ray_interval(S, ro, rd, rmint, rmaxt, false, mint, maxt)) {
+            if (SCENE_LDS && L.scan)
+                hit = scan_tris<false, false>(L, ro, rd, mint, maxt, slot, hu, hv, ht, cT);
+            else if (SCENE_LDS)
+                hit = traverse<false, false, ANA>(ldsNodes, ldsTris, ro, rd, mint, maxt, stkN, stkD, slot, hu, hv, ht,
+                                                  cN, cT, S.analytic);
+            else
+                hit = traverse<false, false, ANA>((glb_node *)S.nodes, (glb_tri *)S.tris, ro, rd, mint, maxt, stkN,
+                                                  stkD, slot, hu, hv, ht, cN, cT, S.analytic);
+        }
+        Hit its = Hit{};
+        bool analytic = false;
+        if (hit) {
+            prim = (SCENE_LDS && L.scan) ? slot : SCENE_LDS ? ldsTris[slot].prim : S.tris[slot].prim;
+            fill_hit<true, ANA>(S, hs, slot, prim, hu, hv, ht, ro, rd, its);
+            if constexpr (ANA) analytic = hs.shapes[its.shape].analytic >= 0;
+        }
+        const float alpha = hit ? 1.0f : 0.0f;   // rRec.alpha: always opacity (multichannel.cpp:181-215)
+
+        const uint32_t nf = FA.num_fields;
+        float *rec = nullptr;
+        if (L.samples) {
+            const uint32_t pixIdx = (uint32_t)(py - (int)L.y0) * L.width + (uint32_t)(px - (int)L.x0);
+            rec = L.samples + ((size_t)pixIdx * L.spp + j) * FA.record_floats;
+            rec[0] = sx; rec[1] = sy; rec[2] = alpha; rec[3] = hit ? 1.0f : 0.0f;
+        }
+        const size_t slot0 = film_slot(L, jj, pix);
+        const size_t fieldSlots = (size_t)(FA.contrib_stride / (L.gather ? 8u : 4u));
+        for (uint32_t f = 0; f < nf; ++f) {
+            f3 r = mk(FA.undefined[f][0], FA.undefined[f][1], FA.undefined[f][2]);
+            if (hit) {
+                switch (FA.field[f]) {   // FieldIntegrator::Li (field.cpp:132-174)
+                    case MTSG_FIELD_POSITION: r = its.p; break;
+                    case MTSG_FIELD_REL_POSITION: r = xf_point(FA.world_to_cam, its.p); break;
+                    case MTSG_FIELD_DISTANCE: r = mk(its.t, its.t, its.t); break;
+                    case MTSG_FIELD_GEO_NORMAL: r = its.geoN; break;
+                    case MTSG_FIELD_SH_NORMAL: r = its.sh.n; break;
+                    case MTSG_FIELD_UV: r = mk(its.u, its.v, 0.0f); break;
+                    case MTSG_FIELD_ALBEDO: r = field_albedo(S, ((GBsdf *)S.bsdfs)[hs.shapes[its.shape].bsdf], its); break;
+                    case MTSG_FIELD_SHAPE_INDEX: { const float s = (float)its.shape; r = mk(s, s, s); break; }
+                    default: {   // MTSG_FIELD_PRIM_INDEX: the triangle within its mesh; KNoTriangleFlag otherwise
+                        const float p = analytic ? (float)0xffffffffu : (float)(prim - FA.shape_first[its.shape]);
+                        r = mk(p, p, p);
+                    }
+                }
+            }
+            // block->put(samplePos, temp) with temp = {.., alpha, 1} (multichannel.cpp:207-217)
+            const float val[5] = {r.x, r.y, r.z, alpha, 1.0f};
+            film_record<false>(L, slot0 + f * fieldSlots, px, py, sx, sy, val, alpha != 0.0f, FA.spill[f]);
+            if (rec) { rec[4 + 3 * f] = r.x; rec[5 + 3 * f] = r.y; rec[6 + 3 * f] = r.z; }
+        }
+        cSamples++;
+        if (smp.err) cErr++;
+    }
+    atomicAdd(L.counters + 0, cSamples);
+    atomicAdd(L.counters + 1, cSamples);   // one closest-hit ray per sample
+    if (cErr) atomicAdd(L.counters + 6, cErr);
+}
+
+// this object's view of the launch record (capi.cpp launch_layout_error)
+extern "C" uint32_t mtsg_launch_bytes_field_kernel() { return (uint32_t)sizeof(MtsgLaunch); }
+
+size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // path_kernel.hip: the same LDS layout
+
+template <int FEAT>
+static hipError_t launch_field_f(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream) {
+    const size_t lds = mtsg_path_lds_bytes(L);
+    if (L.scene_lds) hipLaunchKernelGGL((field_kernel<true, FEAT>), dim3(grid), dim3(BLOCK), lds, stream, L, FA);
+    else hipLaunchKernelGGL((field_kernel<false, FEAT>), dim3(grid), dim3(BLOCK), lds, stream, L, FA);
+    return hipGetLastError();
+}
+
+hipError_t mtsg_launch_field(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream) {
+    if (L.ana) return launch_field_f<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, FA, grid, stream);
+    return launch_field_f<MTSG_FEAT_EXT>(L, FA, grid, stream);
+}
+
+int mtsg_field_occupancy(const MtsgLaunch &L, int *bpc) {
+    const size_t lds = mtsg_path_lds_bytes(L);
+#define MTSG_FIELD_OCC(LDS, F) (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(bpc, field_kernel<LDS, F>, BLOCK, lds)
+    if (L.ana) return L.scene_lds ? MTSG_FIELD_OCC(true, MTSG_FEAT_EXT | MTSG_FEAT_ANA) : MTSG_FIELD_OCC(false, MTSG_FEAT_EXT | MTSG_FEAT_ANA);
+    return L.scene_lds ? MTSG_FIELD_OCC(true, MTSG_FEAT_EXT) : MTSG_FIELD_OCC(false, MTSG_FEAT_EXT);
+#undef MTSG_FIELD_OCC
+}

@@ -16,6 +16,9 @@
 //
 // One thread per output pixel, grid-stride; 20 B read + C * (2|4) B written
 // per pixel -- an HBM-bound streaming kernel.
+//
+// develop_multi_kernel: the same for a film with several pixel formats (the
+// multichannel integrator's), Bitmap::convertMultiSpectrumAlphaWeight.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -103,7 +106,82 @@ hipError_t launch_p(int comp, const float *film, uint32_t full_w, uint32_t borde
     return hipErrorInvalidValue;
 }
 
+// hdrfilm with several pixel formats: Bitmap::convertMultiSpectrumAlphaWeight
+// (src/libcore/bitmap.cpp:1608-1683).  Per pixel invWeight = w == 0 ? 0 : 1/w and
+// alpha = a * invWeight from film 0; film i's value = rgb * invWeight goes through pixel
+// format i (luminance and XYZ of the weighted value), then every channel through
+// convertScalar with multiplier 1.  One thread per pixel; formats are launch data.
+struct MultiArgs {
+    const float *film[MTSGPU_MAX_FIELDS + 1];
+    int32_t pix[MTSGPU_MAX_FIELDS + 1];
+    uint32_t n, channels;
+};
+
+template <int COMP>
+__global__ __launch_bounds__(DEV_BLOCK) void develop_multi_kernel(MultiArgs A, uint32_t full_w, uint32_t border,
+                                                                  uint32_t w, uint32_t h,
+                                                                  typename CompT<COMP>::T *__restrict__ out) {
+    const size_t n = (size_t)w * h;
+    for (size_t i = (size_t)blockIdx.x * DEV_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * DEV_BLOCK) {
+        const uint32_t y = (uint32_t)(i / w), x = (uint32_t)(i - (size_t)y * w);
+        const size_t src = ((size_t)(y + border) * full_w + (x + border)) * 5;
+        const float weight = A.film[0][src + 4];
+        const float inv = weight == 0.0f ? 0.0f : 1.0f / weight;
+        const float alpha = A.film[0][src + 3] * inv;
+        typename CompT<COMP>::T *o = out + i * A.channels;
+        for (uint32_t f = 0; f < A.n; ++f) {
+            const float *px = A.film[f] + src;
+            const float v0 = px[0] * inv, v1 = px[1] * inv, v2 = px[2] * inv;
+            const int pf = A.pix[f];
+            if (pf == MTSGPU_PIX_LUMINANCE || pf == MTSGPU_PIX_LUMINANCE_ALPHA) {
+                *o++ = conv<COMP>(v0 * 0.212671f + v1 * 0.715160f + v2 * 0.072169f, 1.0f);
+            } else if (pf == MTSGPU_PIX_RGB || pf == MTSGPU_PIX_RGBA) {
+                *o++ = conv<COMP>(v0, 1.0f);
+                *o++ = conv<COMP>(v1, 1.0f);
+                *o++ = conv<COMP>(v2, 1.0f);
+            } else {   // Spectrum::toXYZ (spectrum.cpp:229-234)
+                *o++ = conv<COMP>(v0 * 0.412453f + v1 * 0.357580f + v2 * 0.180423f, 1.0f);
+                *o++ = conv<COMP>(v0 * 0.212671f + v1 * 0.715160f + v2 * 0.072169f, 1.0f);
+                *o++ = conv<COMP>(v0 * 0.019334f + v1 * 0.119193f + v2 * 0.950227f, 1.0f);
+            }
+            if (pf == MTSGPU_PIX_LUMINANCE_ALPHA || pf == MTSGPU_PIX_RGBA || pf == MTSGPU_PIX_XYZA)
+                *o++ = conv<COMP>(alpha, 1.0f);
+        }
+    }
+}
+
 }  // namespace
+
+int mtsg_develop_channels(int pixel_format);
+
+hipError_t mtsg_launch_develop_multi(const mtsgpu_develop_multi_params &P, const float *const *films, void *out,
+                                     int num_cus, hipStream_t s) {
+    MultiArgs A;
+    A.n = P.num_films;
+    A.channels = 0;
+    for (uint32_t f = 0; f < MTSGPU_MAX_FIELDS + 1; ++f) {
+        A.film[f] = f < P.num_films ? films[f] : nullptr;
+        A.pix[f] = f < P.num_films ? P.pixel_format[f] : 0;
+        if (f < P.num_films) A.channels += (uint32_t)mtsg_develop_channels(P.pixel_format[f]);
+    }
+    const uint32_t b = P.border, w = P.film_width - 2 * b, h = P.film_height - 2 * b;
+    const size_t n = (size_t)w * h;
+    const size_t want = (n + DEV_BLOCK - 1) / DEV_BLOCK, cap = (size_t)std::max(num_cus, 1) * 16;
+    const int grid = (int)std::max<size_t>(1, std::min(want, cap));
+    switch (P.component_format) {
+        case MTSGPU_COMP_FLOAT16:
+            develop_multi_kernel<MTSGPU_COMP_FLOAT16><<<grid, DEV_BLOCK, 0, s>>>(A, P.film_width, b, w, h, (uint16_t *)out);
+            break;
+        case MTSGPU_COMP_FLOAT32:
+            develop_multi_kernel<MTSGPU_COMP_FLOAT32><<<grid, DEV_BLOCK, 0, s>>>(A, P.film_width, b, w, h, (float *)out);
+            break;
+        case MTSGPU_COMP_UINT32:
+            develop_multi_kernel<MTSGPU_COMP_UINT32><<<grid, DEV_BLOCK, 0, s>>>(A, P.film_width, b, w, h, (uint32_t *)out);
+            break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 int mtsg_develop_channels(int pixel_format) {
     switch (pixel_format) {

@@ -85,7 +85,10 @@ struct MtsgBsdf {            // configured BSDF (after ctor + configure)
     float alpha_u, alpha_v;  // texture average, clamped (microfacet.h:89-97)
     float eta, inv_eta;      // roughdielectric / roughplastic
     float refl[3], spec_r[3], spec_t[3], eta3[3], k3[3];
-    float pad;
+    // roughplastic with a constant alpha: m_externalRoughTransmittance->evalDiffuse(alpha), the
+    // factor of getDiffuseReflectance (roughplastic.cpp:309-315); with a textured alpha the external
+    // table's diffuse slice follows the internal one in rtrans (rt_int + rt_alpha, rt_alpha values)
+    float ftr_ext;
     // roughplastic (roughplastic.cpp:255-300): refl = diffuseReflectance
     float inv_eta2, spec_weight;
     int32_t nonlinear;
@@ -347,6 +350,25 @@ struct MtsgLaunch {
     uint32_t one_emitter;                  // the emitter CDF is {0.0f, 1.0f} bit for bit: emitter 0 with pdf 1
     const float *face_n;                   // 3 per primitive: unit face normals, staged in LDS with a small scene
                                            // (HitSrc<true>::fn; scene_build.cpp mtsg_face_normal)
+};
+
+// The field pass (field_kernel.hip; FieldIntegrator::Li, integrators/misc/field.cpp:124-177):
+// the second argument of field_kernel, next to the launch record.  One primary ray per
+// sample serves every listed field; field f's records go to contrib + f * contrib_stride
+// floats (film_slot within), its sample values to samples[4 + 3f ..].
+#define MTSG_MAX_FIELDS 8
+enum { MTSG_FIELD_POSITION = 0, MTSG_FIELD_REL_POSITION = 1, MTSG_FIELD_DISTANCE = 2, MTSG_FIELD_GEO_NORMAL = 3,
+       MTSG_FIELD_SH_NORMAL = 4, MTSG_FIELD_UV = 5, MTSG_FIELD_ALBEDO = 6, MTSG_FIELD_SHAPE_INDEX = 7,
+       MTSG_FIELD_PRIM_INDEX = 8, MTSG_FIELD_COUNT = 9 };   // = MTSGPU_FIELD_* = FieldIntegrator::EField
+struct MtsgFieldArgs {
+    uint32_t num_fields;
+    int32_t field[MTSG_MAX_FIELDS];
+    float undefined[MTSG_MAX_FIELDS][3];   // m_undefined: the value where the ray hits nothing
+    float world_to_cam[16];                // the sensor's world transform inverted (Transform::inverse)
+    const uint32_t *shape_first;           // first global primitive of each shape (its.primIndex = prim - first)
+    uint64_t contrib_stride;               // floats between two fields' record arrays
+    double *spill[MTSG_MAX_FIELDS];        // box filter: each field's neighbour-splat film (MtsgLaunch::film_spill)
+    uint32_t record_floats;                // 4 + 3 * num_fields
 };
 
 #ifndef MTSG_MIN_RUNS

@@ -362,6 +362,10 @@ int configure_roughplastic(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::vector<f
     rt.insert(rt.end(), ext.trans.begin(), ext.trans.end());
     b.rt_int = (int32_t)rt.size();
     rt.insert(rt.end(), in.diff.begin(), in.diff.end());
+    // getDiffuseReflectance's m_externalRoughTransmittance->evalDiffuse(alpha) (roughplastic.cpp:
+    // 309-315): the value for a constant alpha, the table's diffuse slice for a textured one
+    if (d.alpha_tex.type == MTSGPU_TEX_NONE) b.ftr_ext = mtsg_rtrans_eval_diffuse(ext, b.alpha_u);
+    else rt.insert(rt.end(), ext.diff.begin(), ext.diff.end());
     return MTSGPU_OK;
 }
 
@@ -1082,6 +1086,16 @@ const std::vector<uint32_t> &mtsg_sobol_matrices() {
     return M;
 }
 
+// Matrix4x4::invert (matrix.inl:138-193) of a row-major 4x4: the inverse a Transform built
+// from a matrix carries (transform.h:54-60); false for a singular matrix
+bool mtsg_invert4(const float *m16, float *inv16) {
+    M4 a, r;
+    std::memcpy(&a.m[0][0], m16, sizeof a.m);
+    if (!invert(a, r)) return false;
+    std::memcpy(inv16, &r.m[0][0], sizeof r.m);
+    return true;
+}
+
 // fill_hit's face normal (dpath.h; skdtree.h:355-360): cross(p1 - p0, p2 - p0) as dmath.h
 // forms it, its length by a correctly rounded sqrt, 1 / length, three products; left
 // as it is when it is all zero.  (This unit is built with -ffp-contract=off.)
@@ -1385,7 +1399,8 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
             }
         }
         sh.has_normals = hasNormals ? 1 : 0;
-        sh.has_uv = (S.ext && m.texcoords) ? 1 : 0;
+        // (read by the kernels that form its.uv: the EXT variants and the field pass)
+        sh.has_uv = m.texcoords ? 1 : 0;
         if (sh.has_uv) {
             if (S.texcoords.empty()) S.texcoords.assign((size_t)verts * 2, 0.0f);
             std::memcpy(&S.texcoords[2 * (size_t)voff], m.texcoords, sizeof(float) * 2 * (size_t)nv);

@@ -57,6 +57,7 @@ struct HostScene {
 int mtsg_configure_scene(const mtsgpu_scene_desc *desc, HostScene &out, std::string &err);
 // the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dpath.h)
 void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n);
+bool mtsg_invert4(const float *m16, float *inv16);   // Matrix4x4::invert, row-major
 void mtsg_build_qnodes(HostScene &S);   // host export only (mtsgpu_bvh_host)
 int mtsg_configure_filter(int32_t type, float param, MtsgFilter &f, std::string &err);
 // Sobol: 1024 x 52 matrices regenerated from the Joe-Kuo parameters, and the

@@ -8,6 +8,10 @@ Mirrors HDRFilm (src/films/hdrfilm.cpp:205-360, 481-535):
 - `develop()` runs on the device: libmtsgpu's `mtsgpu_develop` kernel divides
   by the filter weights and converts to the pixel/component format exactly as
   Bitmap::convert does (src/libcore/fmtconv.cpp:955-1030, 1137-1160).
+- Several pixel formats with their channel names (hdrfilm.cpp:243-292, the storage
+  of a `multichannel` render): `develop()` then takes one film per format and runs
+  `mtsgpu_develop_multi` (Bitmap::convertMultiSpectrumAlphaWeight, bitmap.cpp:
+  1595-1683); OpenEXR only, written as the named channels.
 - The file writers follow Bitmap::writeOpenEXR / writePFM / writeRGBE
   (src/libcore/bitmap.cpp:3180-3336, 3816-3855, 3691-3750).  OpenEXR files are
   scanline images with ZIP compression (the Imf::Header default), PIZ-free, so
@@ -74,13 +78,19 @@ class HDRFilm:
             if f not in PIXEL_FORMATS:
                 raise ValueError('The "pixelFormat" parameter must either be equal to "luminance", '
                                  '"luminanceAlpha", "rgb", "rgba", "xyz", "xyza", "spectrum", or "spectrumAlpha"!')
-        if len(fmts) != 1:
-            # EMultiSpectrumAlphaWeight storage only arises with multichannel integrators
-            raise NotImplementedError('multi-format hdrfilm output (needs the "multichannel" integrator)')
         self.componentFormat = self.componentFormat.lower()
         if self.componentFormat not in COMPONENT_FORMATS:
             raise ValueError('The "componentFormat" parameter must either be equal to "float16", "float32", '
                              'or "uint32"!')
+        if len(fmts) != 1:
+            # EMultiSpectrumAlphaWeight storage (the multichannel integrator's): one pixel format and
+            # one channel-name prefix per nested integrator (hdrfilm.cpp:243-292, storage :351-356),
+            # OpenEXR only
+            self._fmts = fmts
+            self._fmt = fmts[0]
+            self._channels = [n + '.' + c for f, n in zip(fmts, names) for c in PIXEL_FORMATS[f][1]]
+            self.banner = False                # (the banner is stamped on single-format output only)
+            return
         fmt = fmts[0]
         if self.fileFormat == 'rgbe':          # hdrfilm.cpp:314-325
             fmt, self.componentFormat = 'rgb', 'float32'
@@ -89,6 +99,7 @@ class HDRFilm:
                 fmt = 'rgb'
             self.componentFormat = 'float32'
         self._fmt = fmt
+        self._fmts = [fmt]
         prefix = names[0] + '.' if names else ''
         self._channels = [prefix + c for c in PIXEL_FORMATS[fmt][1]]
 
@@ -98,13 +109,28 @@ class HDRFilm:
         return self._fmt
 
     @property
+    def pixel_formats(self):
+        """Every pixel format: one per nested integrator of a multichannel render."""
+        return list(self._fmts)
+
+    @property
     def channel_names(self):
         return list(self._channels)
 
     @property
     def hasAlpha(self):
-        """HDRFilm::hasAlpha (hdrfilm.cpp:539-548)."""
-        return self._fmt in ('luminancealpha', 'rgba', 'xyza')
+        """HDRFilm::hasAlpha (hdrfilm.cpp:539-548): any format with an alpha channel."""
+        return any(f in ('luminancealpha', 'rgba', 'xyza') for f in self._fmts)
+
+    def develop_multi_params(self, film_shape, border):
+        p = abi.DevelopMultiParams()
+        p.film_height, p.film_width = int(film_shape[0]), int(film_shape[1])
+        p.border = int(border)
+        p.num_films = len(self._fmts)
+        for i, f in enumerate(self._fmts):
+            p.pixel_format[i] = PIXEL_FORMATS[f][0]
+        p.component_format = COMPONENT_FORMATS[self.componentFormat][0]
+        return p
 
     def develop_params(self, film_shape, border):
         p = abi.DevelopParams()
@@ -117,11 +143,16 @@ class HDRFilm:
 
     def output_array(self, film_shape, border):
         h, w = film_shape[0] - 2 * border, film_shape[1] - 2 * border
-        return np.empty((h, w, len(PIXEL_FORMATS[self._fmt][1])), COMPONENT_FORMATS[self.componentFormat][1])
+        return np.empty((h, w, len(self.channel_names)), COMPONENT_FORMATS[self.componentFormat][1])
 
     def develop(self, ctx, film, border):
         """HDRFilm::develop's conversion on the device: `film` is the (H+2b, W+2b, 5)
-        float32 film mtsgpu_render returned; returns (H, W, C) in the component dtype."""
+        float32 film mtsgpu_render returned -- with several pixel formats the
+        (N, H+2b, W+2b, 5) films of a multichannel render, developed as
+        Bitmap::convertMultiSpectrumAlphaWeight does (hdrfilm.cpp:488-494); returns
+        (H, W, C) in the component dtype."""
+        if len(self._fmts) != 1:
+            return ctx.develop_multi(film, border, self)
         if self.banner:
             _warn_banner()
         return ctx.develop(film, border, self)

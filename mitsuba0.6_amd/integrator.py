@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import LIB_PATH, abi
-from .scene import PathIntegrator, film_border
+from .scene import FieldIntegrator, MultiChannelIntegrator, PathIntegrator, film_border
 
 
 class NativeUnavailable(RuntimeError):
@@ -33,7 +33,8 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_group_destroy', 'mtsgpu_trace_rays_ex', 'mtsgpu_debug_kdtree', 'mtsgpu_kdtree_host', 'mtsgpu_debug_libm',
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
            'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
-           'mtsgpu_face_normals_host']
+           'mtsgpu_face_normals_host', 'mtsgpu_render_fields', 'mtsgpu_render_fields_device', 'mtsgpu_develop_multi',
+           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host']
 
 _lib = None
 
@@ -94,6 +95,15 @@ def load_library(path=None):
         L.mtsgpu_lookup_host.argtypes = [C.c_uint32, C.c_uint64, P(C.c_uint32), C.c_size_t, P(C.c_uint64)]
     if hasattr(L, 'mtsgpu_face_normals_host'):
         L.mtsgpu_face_normals_host.argtypes = [P(abi.SceneDesc), P(C.c_float), P(C.c_float), C.c_size_t, P(C.c_uint32)]
+    if hasattr(L, 'mtsgpu_render_fields'):   # added within ABI 8 as well (field / multichannel integrators)
+        L.mtsgpu_render_fields.argtypes = [C.c_void_p, P(abi.RenderParams), P(abi.FieldDesc), C.c_uint32, P(C.c_float),
+                                           P(C.c_float), P(abi.Stats)]
+        L.mtsgpu_render_fields_device.argtypes = [C.c_void_p, P(abi.RenderParams), P(abi.FieldDesc), C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, P(abi.Stats)]
+        L.mtsgpu_develop_multi.argtypes = [C.c_void_p, P(abi.DevelopMultiParams), P(C.c_void_p), C.c_void_p]
+        L.mtsgpu_develop_multi_device.argtypes = [C.c_void_p, P(abi.DevelopMultiParams), P(C.c_void_p), C.c_void_p,
+                                                  C.c_void_p]
+        L.mtsgpu_albedo_factors_host.argtypes = [P(abi.SceneDesc), P(C.c_float), C.c_char_p, C.c_size_t]
     L.mtsgpu_group_create.argtypes = [P(C.c_int), C.c_int, P(C.c_void_p)]
     L.mtsgpu_group_size.argtypes = [C.c_void_p]
     L.mtsgpu_group_upload_scene.argtypes = [C.c_void_p, P(abi.SceneDesc)]
@@ -120,6 +130,21 @@ def check_scene(scene):
     rc = L.mtsgpu_check_scene(C.byref(d), buf, 1024)
     if rc != 0:
         raise MtsgpuError(rc, buf.value.decode())
+
+
+def albedo_factors_host(scene):
+    """Per BSDF the scalar factor of its getDiffuseReflectance, configured on the host
+    without a device (mtsgpu_albedo_factors_host): plastic 1 - fdrExt, roughplastic with
+    a constant alpha the external table's evalDiffuse(alpha) (-1 for a textured alpha),
+    1 for diffuse, 0 otherwise; in the order of scene.flat_bsdfs()."""
+    L = load_library()
+    d = scene.desc()
+    out = np.zeros(max(1, d.num_bsdfs), np.float32)     # one per BSDF of scene.flat_bsdfs()
+    buf = C.create_string_buffer(512)
+    rc = L.mtsgpu_albedo_factors_host(C.byref(d), abi.fptr(out), buf, 512)
+    if rc != 0:
+        raise MtsgpuError(rc, buf.value.decode())
+    return out[:d.num_bsdfs]
 
 
 KD_KEYS = ('nodes', 'indices', 'inner', 'leaves', 'nonempty_leaves', 'retracted', 'pruned', 'max_depth')
@@ -265,7 +290,7 @@ class Context:
         name is the template as rocprofv3 reports it, e.g.
         'path_kernel<false, false, 336, 4>'; None after a wavefront-engine render."""
         c = self.debug_counters()[15]
-        if c & (1 << 16):
+        if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
             return None
         feat = (c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0)
         instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
@@ -303,6 +328,8 @@ class Context:
         (the wavefront engine tracing through the reference's kd-tree).
         row = (row_block, row_stride, row_phase); tile_shard: row_stride/row_phase
         select 8x8 tiles (MTSGPU_FLAG_TILE_SHARD) instead of row blocks."""
+        if isinstance(integ, MultiChannelIntegrator):
+            return self._render_multichannel(integ, window, samples, row, traversal_stats, engine, tile_shard)
         sc = self.scene
         W, H = sc.sensor.width, sc.sensor.height
         x0, y0, w, h = window if window else (integ.crop or (0, 0, W, H))
@@ -320,6 +347,70 @@ class Context:
                                           smp.ctypes.data_as(C.POINTER(C.c_float)) if samples else None,
                                           C.byref(st)))
         return film, smp, st.as_dict()
+
+    def render_fields(self, integ, fields, window=None, samples=False, row=(0, 1, 0), tile_shard=False):
+        """The field pass (mtsgpu_render_fields): `fields` is a list of FieldIntegrators (or
+        field names), `integ` supplies the sampler, filter and crop settings (any integrator
+        here; its integrator properties are ignored).  The primary ray of every sample is
+        traced once for all fields.  Returns (films (N, H+2b, W+2b, 5) float32, one
+        {f.r, f.g, f.b, alpha, w} film per field; per-sample records (w*h*spp, 4 + 3N)
+        {samplePos.x, samplePos.y, alpha, hit, f0.rgb, ...} or None; stats dict)."""
+        fields = [f if isinstance(f, FieldIntegrator) else FieldIntegrator(f) for f in fields]
+        sc = self.scene
+        W, H = sc.sensor.width, sc.sensor.height
+        x0, y0, w, h = window if window else (integ.crop or (0, 0, W, H))
+        p = integ.params(W, H, x0, y0, w, h, row[0], row[1], row[2])
+        if tile_shard:
+            p.flags |= abi.FLAG_TILE_SHARD
+        n = len(fields)
+        descs = (abi.FieldDesc * max(1, n))(*[f.to_desc() for f in fields])
+        b = film_border(integ.rfilter, integ.rfilterParam)
+        films = np.zeros((max(1, n), H + 2 * b, W + 2 * b, 5), np.float32)
+        smp = np.zeros((w * h * integ.sampleCount, 4 + 3 * n), np.float32) if samples else None
+        st = abi.Stats()
+        self._check(self.L.mtsgpu_render_fields(self.h, C.byref(p), descs, n, abi.fptr(films),
+                                                 abi.fptr(smp) if samples else None, C.byref(st)))
+        return films[:n], smp, st.as_dict()
+
+    def _render_multichannel(self, integ, window, samples, row, traversal_stats, engine, tile_shard):
+        """MultiChannelIntegrator: the radiance integrator's normal render with an alpha
+        channel, then the field pass at the same sample positions.  Returns (films
+        (N, H+2b, W+2b, 5) in child order, (colour records or None, field records) or
+        None, stats of the colour render plus 'field_kernel_ms' -- or of the field pass
+        when there is no radiance integrator)."""
+        rad = integ.radiance
+        film_c = smp_c = st = None
+        if rad is not None:
+            film_c, smp_c, st = self.render(rad, window, samples, row, traversal_stats, engine, tile_shard)
+        flds = integ.fields
+        films_f = smp_f = None
+        if flds:
+            films_f, smp_f, st_f = self.render_fields(integ, flds, window, samples, row, tile_shard)
+            if st is None:
+                st = st_f
+            st['field_kernel_ms'] = st_f['kernel_ms']
+        out, k = [], 0
+        for c in integ.children:
+            if isinstance(c, FieldIntegrator):
+                out.append(films_f[k])
+                k += 1
+            else:
+                out.append(film_c)
+        return np.stack(out), ((smp_c, smp_f) if samples else None), st
+
+    def develop_multi(self, films, border, hdrfilm):
+        """hdrfilm develop with several pixel formats (mtsgpu_develop_multi): `films`
+        (N, H+2b, W+2b, 5) float32, one per pixel format of `hdrfilm`; film 0 supplies
+        alpha and weight.  Returns (H, W, C) in hdrfilm's component dtype, channels in
+        format order (hdrfilm.channel_names)."""
+        films = np.ascontiguousarray(films, np.float32)
+        if films.ndim != 4 or films.shape[3] != 5 or films.shape[0] != len(hdrfilm.pixel_formats):
+            raise ValueError('develop_multi: films must be (N, H+2b, W+2b, 5) float32, one per pixel format')
+        p = hdrfilm.develop_multi_params(films.shape[1:], border)
+        out = hdrfilm.output_array(films.shape[1:], border)
+        ptrs = (C.c_void_p * films.shape[0])(*[films[i].ctypes.data for i in range(films.shape[0])])
+        self._check(self.L.mtsgpu_develop_multi(self.h, C.byref(p), ptrs, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def render_device(self, integ, film_ptr, stream_ptr=None, window=None, row=(0, 1, 0), engine=None,
                       tile_shard=False):
@@ -476,9 +567,11 @@ class DeviceGroup:
 class PathTracer(PathIntegrator):
     """The `path` integrator (MIPathTracer) running on MI355X."""
 
-    def render(self, scene, ctx=None):
+    def render(self, scene, ctx=None, integrator=None):
+        """Renders with this integrator, or with `integrator` (e.g. a
+        MultiChannelIntegrator: the films then come in child order, (N, H+2b, W+2b, 5))."""
         ctx = ctx or Context()
         if ctx.scene is not scene:
             ctx.upload(scene)
-        film, _, stats = ctx.render(self)
+        film, _, stats = ctx.render(integrator if integrator is not None else self)
         return film, stats

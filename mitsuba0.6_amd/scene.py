@@ -259,6 +259,21 @@ class Scene:
         """Primitives of the acceleration structure (an analytic shape counts one)."""
         return sum(1 if m.analytic else int(m.indices.shape[0]) for m in self.meshes)
 
+    def flat_bsdfs(self):
+        """The BSDF list as desc() packs it: twosided's nested BSDFs go after the scene's own
+        (mesh indices stay valid); (list, {twosided index: [nested indices]})."""
+        flat = list(self.bsdfs)
+        nested_idx = {}
+        for i, b in enumerate(self.bsdfs):
+            if b.type == 'twosided':
+                if not 1 <= len(b.nested) <= 2:
+                    raise ValueError('twosided: one or two nested BSDFs (twosided.cpp:82-87, 161-170)')
+                nested_idx[i] = []
+                for nb in b.nested:
+                    nested_idx[i].append(len(flat))
+                    flat.append(nb)
+        return flat, nested_idx
+
     def desc(self):
         """Pack into abi.SceneDesc; the returned object keeps every buffer alive."""
         keep = []
@@ -295,17 +310,7 @@ class Scene:
             md[i].num_triangles = idx.shape[0]
             md[i].bsdf, md[i].emitter = m.bsdf, m.emitter
             md[i].face_normals, md[i].flip_normals = int(m.faceNormals), int(m.flipNormals)
-        # twosided's nested BSDFs go after the scene's own (mesh indices stay valid)
-        flat = list(self.bsdfs)
-        nested_idx = {}
-        for i, b in enumerate(self.bsdfs):
-            if b.type == 'twosided':
-                if not 1 <= len(b.nested) <= 2:
-                    raise ValueError('twosided: one or two nested BSDFs (twosided.cpp:82-87, 161-170)')
-                nested_idx[i] = []
-                for nb in b.nested:
-                    nested_idx[i].append(len(flat))
-                    flat.append(nb)
+        flat, nested_idx = self.flat_bsdfs()
         bd = (abi.BsdfDesc * max(1, len(flat)))()
         for i, b in enumerate(flat):
             bdi = b.to_desc()
@@ -426,6 +431,95 @@ class DirectIntegrator(PathIntegrator):
         p = super().params(*a, **kw)
         p.integrator = abi.INTEGRATOR_DIRECT
         p.emitter_samples, p.bsdf_samples = self.emitterSamples, self.bsdfSamples
+        return p
+
+
+# FieldIntegrator::EField (field.cpp:57-67) = MTSGPU_FIELD_*
+FIELDS = ('position', 'relPosition', 'distance', 'geoNormal', 'shNormal', 'uv', 'albedo', 'shapeIndex',
+          'primIndex')
+
+
+@dataclass
+class FieldIntegrator:
+    """The reference `field` plugin (FieldIntegrator, src/integrators/misc/field.cpp:
+    55-187): one field of the camera ray's intersection record per sample;
+    `undefined` (a float or three) is the value where the ray hits nothing."""
+    field: str
+    undefined: object = 0.0
+
+    def __post_init__(self):
+        if self.field not in FIELDS:       # field.cpp:91-93
+            raise ValueError("Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', "
+                             "'geoNormal', 'shNormal', 'primIndex', 'shapeIndex', or 'uv'!")
+        u = np.asarray(self.undefined, np.float32).reshape(-1)
+        if u.size not in (1, 3):
+            raise ValueError("'undefined' must be a float or a spectrum of three values")
+        self.undefined = tuple(float(x) for x in (u if u.size == 3 else np.repeat(u, 3)))
+
+    def to_desc(self):
+        d = abi.FieldDesc()
+        d.field = FIELDS.index(self.field)
+        d.undefined[:] = self.undefined
+        return d
+
+
+# the sampler / film settings every integrator here carries (the reference keeps them on the sensor)
+_SETTINGS = ('sampleCount', 'scramble', 'rfilter', 'rfilterParam', 'crop', 'film', 'sampler')
+
+
+class MultiChannelIntegrator:
+    """The reference `multichannel` plugin (MultiChannelIntegrator, src/integrators/
+    misc/multichannel.cpp:87-262): several nested integrators run per sample, each
+    into its own channels of the film.  `children` are FieldIntegrators and at most
+    one radiance integrator (path / volpath / direct), at any position.  The sampler
+    and film settings (sampleCount, scramble, sampler, rfilter, rfilterParam, crop,
+    film) are those of the radiance integrator unless given here; alpha is always
+    opacity (renderBlock never strips EOpacity, multichannel.cpp:181-215)."""
+
+    def __init__(self, children, **settings):
+        self.children = list(children)
+        if not self.children:              # multichannel.cpp:131-132
+            raise ValueError('No sub-integrators were supplied to the multi-channel integrator!')
+        for c in self.children:
+            if not isinstance(c, (FieldIntegrator, PathIntegrator)):
+                raise ValueError('multichannel: nested integrators must be field, path, volpath or direct')
+        radiance = [c for c in self.children if isinstance(c, PathIntegrator)]
+        if len(radiance) > 1:
+            # renderBlock hands every nested Li the one sampler (multichannel.cpp:208-214): the
+            # second radiance integrator continues the first one's sampler dimensions, which a
+            # separate render of it cannot reproduce
+            raise NotImplementedError('multichannel: more than one radiance integrator (path / volpath / direct): '
+                                      'in the reference the second one continues the first one\'s sampler '
+                                      'dimensions, which a separate render cannot reproduce')
+        if len(self.children) - len(radiance) > abi.MAX_FIELDS:
+            raise ValueError('multichannel: at most %d field integrators' % abi.MAX_FIELDS)
+        bad = set(settings) - set(_SETTINGS)
+        if bad:
+            raise TypeError('multichannel: unknown settings %s' % sorted(bad))
+        base = radiance[0] if radiance else PathIntegrator()
+        for k in _SETTINGS:
+            setattr(self, k, settings.get(k, getattr(base, k)))
+        self.hasAlpha = True
+        if self.sampler not in SAMPLERS:
+            raise ValueError('sampler "%s" (%s)' % (self.sampler, ', '.join(SAMPLERS)))
+
+    @property
+    def fields(self):
+        return [c for c in self.children if isinstance(c, FieldIntegrator)]
+
+    @property
+    def radiance(self):
+        """The nested radiance integrator with this integrator's sampler and film
+        settings and an alpha channel, or None."""
+        import dataclasses
+        for c in self.children:
+            if isinstance(c, PathIntegrator):
+                return dataclasses.replace(c, hasAlpha=True, **{k: getattr(self, k) for k in _SETTINGS})
+        return None
+
+    def params(self, *a, **kw):
+        """Render parameters of the field pass (its integrator fields are ignored)."""
+        p = PathIntegrator(hasAlpha=True, **{k: getattr(self, k) for k in _SETTINGS}).params(*a, **kw)
         return p
 
 

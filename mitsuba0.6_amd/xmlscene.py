@@ -15,7 +15,8 @@ Plugins:
 - integrators `path` and `volpath` (maxDepth, rrDepth, strictNormals,
   hideEmitters; volpath without media) and
   `direct` (shadingSamples, emitterSamples, bsdfSamples, strictNormals,
-  hideEmitters).
+  hideEmitters); `multichannel` with nested `field` (field, undefined) and at
+  most one of `path` / `volpath` / `direct`.
 - sensor `perspective` (fov/fovAxis or focalLength, near/farClip, toWorld),
   with sampler `sobol` (sampleCount, scramble) or `independent` (sampleCount;
   the default without a <sampler>), film `hdrfilm` or `mfilm` (size, crop
@@ -39,8 +40,8 @@ import numpy as np
 from .film import HDRFilm, MFilm, load_bitmap, read_pfm, write_pfm  # noqa: F401  (Bitmap readers/writers)
 from .obj import load_obj, srgb_to_linear, strtof
 from .ply import load_ply
-from .scene import (BSDF, Checkerboard, DirectIntegrator, Emitter, Mesh, PathIntegrator, Scene, Sensor,
-                    VolpathIntegrator)
+from .scene import (BSDF, Checkerboard, DirectIntegrator, Emitter, FieldIntegrator, Mesh, MultiChannelIntegrator,
+                    PathIntegrator, Scene, Sensor, VolpathIntegrator)
 from .serialized import load_serialized
 from .transform import Transform, _cross, _normalize, normalize_rows
 
@@ -470,9 +471,24 @@ class XMLSceneLoader:
             raise SceneError('the scene has no triangle meshes')
         return Scene(sensor, meshes, bsdfs, emitters, name=os.path.basename(self.path)), integ
 
-    def _integrator(self, p):
+    def _integrator(self, p, nested=False):
         if p is None:
             raise SceneError('no <integrator> (the GPU path implements "path")')
+        if p.plugin == 'multichannel' and not nested:      # multichannel.cpp:87-262
+            kids = [self._integrator(c, nested=True) for _, c in p.children if c.tag == 'integrator']
+            try:
+                return MultiChannelIntegrator(kids)
+            except ValueError as e:
+                raise SceneError(str(e))
+        if p.plugin == 'field' and nested:                 # field.cpp:69-110
+            if 'field' not in p:
+                raise SceneError('Property "field" has not been specified!')
+            try:
+                return FieldIntegrator(p['field'], p.get('undefined', 0.0))
+            except ValueError as e:
+                raise SceneError(str(e))
+        if p.plugin == 'field':
+            raise NotImplementedError('integrator "field" outside a "multichannel" integrator')
         if p.plugin == 'direct':                     # direct.cpp:92-107
             n = int(p.get('shadingSamples', 1))
             return DirectIntegrator(shadingSamples=n, emitterSamples=int(p.get('emitterSamples', n)),
@@ -480,8 +496,8 @@ class XMLSceneLoader:
                                     strictNormals=p.get('strictNormals', False),
                                     hideEmitters=p.get('hideEmitters', False))
         if p.plugin not in ('path', 'volpath'):
-            raise NotImplementedError('integrator "%s" (the GPU path implements "path", "volpath" and "direct")'
-                                      % p.plugin)
+            raise NotImplementedError('integrator "%s" (the GPU path implements "path", "volpath", "direct" and '
+                                      '"multichannel" with nested "field" integrators)' % p.plugin)
         cls = VolpathIntegrator if p.plugin == 'volpath' else PathIntegrator
         return cls(maxDepth=p.get('maxDepth', -1), rrDepth=p.get('rrDepth', 5),
                    strictNormals=p.get('strictNormals', False), hideEmitters=p.get('hideEmitters', False))
@@ -691,22 +707,40 @@ def _bsdf_xml(b, ind, bid=None):
     return L
 
 
+def _integrator_xml(integ, ind):
+    L = []
+    if isinstance(integ, MultiChannelIntegrator):
+        L.append(ind + '<integrator type="multichannel">')
+        for c in integ.children:
+            L += _integrator_xml(c, ind + '  ')
+        L.append(ind + '</integrator>')
+        return L
+    if isinstance(integ, FieldIntegrator):
+        L.append(ind + '<integrator type="field">')
+        L.append(ind + '  <string name="field" value="%s"/>' % integ.field)
+        L.append(ind + '  ' + _rgb('undefined', integ.undefined))
+        L.append(ind + '</integrator>')
+        return L
+    if isinstance(integ, DirectIntegrator):
+        L.append(ind + '<integrator type="direct">')
+        L.append(ind + '  <integer name="emitterSamples" value="%d"/>' % integ.emitterSamples)
+        L.append(ind + '  <integer name="bsdfSamples" value="%d"/>' % integ.bsdfSamples)
+    else:
+        L.append(ind + '<integrator type="%s">' % ('volpath' if isinstance(integ, VolpathIntegrator) else 'path'))
+        L.append(ind + '  <integer name="maxDepth" value="%d"/>' % integ.maxDepth)
+        L.append(ind + '  <integer name="rrDepth" value="%d"/>' % integ.rrDepth)
+    L.append(ind + '  <boolean name="strictNormals" value="%s"/>' % str(bool(integ.strictNormals)).lower())
+    L.append(ind + '  <boolean name="hideEmitters" value="%s"/>' % str(bool(integ.hideEmitters)).lower())
+    L.append(ind + '</integrator>')
+    return L
+
+
 def save_scene(scene, integ, directory, name='scene.xml'):
     """Write `scene` as a Mitsuba 0.6 XML scene (meshes as PLY, envmap as PFM)."""
     os.makedirs(directory, exist_ok=True)
     from .ply import write_ply
     L = ['<?xml version="1.0" encoding="utf-8"?>', '<scene version="0.6.0">']
-    if isinstance(integ, DirectIntegrator):
-        L.append('  <integrator type="direct">')
-        L.append('    <integer name="emitterSamples" value="%d"/>' % integ.emitterSamples)
-        L.append('    <integer name="bsdfSamples" value="%d"/>' % integ.bsdfSamples)
-    else:
-        L.append('  <integrator type="%s">' % ('volpath' if isinstance(integ, VolpathIntegrator) else 'path'))
-        L.append('    <integer name="maxDepth" value="%d"/>' % integ.maxDepth)
-        L.append('    <integer name="rrDepth" value="%d"/>' % integ.rrDepth)
-    L.append('    <boolean name="strictNormals" value="%s"/>' % str(bool(integ.strictNormals)).lower())
-    L.append('    <boolean name="hideEmitters" value="%s"/>' % str(bool(integ.hideEmitters)).lower())
-    L.append('  </integrator>')
+    L += _integrator_xml(integ, '  ')
     s = scene.sensor
     L.append('  <sensor type="perspective">')
     L.append('    <float name="fov" value="%s"/>' % _fmt(s.fov))
@@ -724,7 +758,12 @@ def save_scene(scene, integ, directory, name='scene.xml'):
     mf = isinstance(hf, MFilm)
     L.append('    <film type="%s">' % ('mfilm' if mf else 'hdrfilm'))
     L.append('      <integer name="width" value="%d"/><integer name="height" value="%d"/>' % (s.width, s.height))
-    fmt = hf.pixel_format if hf.hasAlpha == bool(integ.hasAlpha) else ('rgba' if integ.hasAlpha else 'rgb')
+    multi = not mf and len(hf.pixel_formats) != 1
+    if multi:       # one pixel format and channel-name prefix per nested integrator (hdrfilm.cpp:243-292)
+        fmt = ', '.join(hf.pixel_formats)
+        L.append('      <string name="channelNames" value="%s"/>' % hf.channelNames)
+    else:
+        fmt = hf.pixel_format if hf.hasAlpha == bool(integ.hasAlpha) else ('rgba' if integ.hasAlpha else 'rgb')
     L.append('      <string name="pixelFormat" value="%s"/>' % fmt)
     if mf:
         L.append('      <string name="fileFormat" value="%s"/><integer name="digits" value="%d"/>'
