@@ -527,7 +527,9 @@ int mtsgpu_debug_scene_info(mtsgpu_ctx *ctx, uint32_t *info4);
 int mtsgpu_debug_libm(mtsgpu_ctx *ctx, int fn, const float *a, const float *b, float *out, size_t n,
                       uint32_t first);
 /* the 16 raw device counters of the last render (samples, rays, shadow rays,
-   path lengths, node visits, TriAccel tests, dimension errors, hits, -, NEE
+   path lengths, node visits, TriAccel tests, dimension errors, hits, 8: the
+   launches the render's sample count was split into -- the chunks of the
+   per-sample record budget, written by the host, 1 when all samples fit --, NEE
    samples, Sobol HBM words, diagnostic section cycles 11-14), and in 15 the
    kernel that ran: the megakernel's feature set (MTSG_FEAT_* bits of
    csrc/layout.h, BSDF-set bits included) | waves/SIMD << 8 | scene in LDS << 12,

@@ -1031,8 +1031,10 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
         }
     }
     if ((e = hipEventRecord(ctx->ev0, stream)) != hipSuccess) return hip_fail(ctx, e, "event");
+    unsigned long long launchedChunks = 0;   // (debug counter 8)
     for (uint32_t j0 = 0; j0 < P->spp; j0 += chunk) {
         if (P->cancel && *P->cancel) break;
+        ++launchedChunks;
         L.j0 = j0;
         L.chunk_spp = std::min(chunk, P->spp - j0);
         L.num_items = (uint64_t)L.chunk_spp * L.num_pixels;
@@ -1072,6 +1074,8 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
         return hip_fail(ctx, e, "sample copy");
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(ctx, e, "path kernel");
     std::memcpy(ctx->last_counters, hc, sizeof hc);
+    // counter 8: the launches the sample count was split into (the chunk loop's iterations)
+    ctx->last_counters[8] = launchedChunks;
     // counter 15: which kernel ran -- for the megakernel path_kernel<INSTR, SCENE_LDS, FEAT, WAVES>:
     // FEAT's low 8 bits | WAVES << 8 | SCENE_LDS << 12 | INSTR << 13 | (FEAT & NOSTRICT) << 14 (the
     // set kernels' strictNormals-free build) | (FEAT & NOREFN) << 15; 1 << 16 for the wavefront engine

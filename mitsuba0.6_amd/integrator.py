@@ -284,6 +284,10 @@ class Context:
         self._check(self.L.mtsgpu_debug_counters(self.h, out))
         return list(out)
 
+    def launch_chunks(self):
+        """The launches the last render's sample count was split into (debug counter 8)."""
+        return self.debug_counters()[8]
+
     def kernel_variant(self):
         """The megakernel instantiation the last render launched, decoded from debug
         counter 15 (capi.cpp): {'instr', 'scene_lds', 'feat', 'waves', 'name'}, where
@@ -322,12 +326,14 @@ class Context:
         raise ValueError('engine must be None, "wavefront", "megakernel" or "kdtree"')
 
     def render(self, integ, window=None, samples=False, row=(0, 1, 0), traversal_stats=False, engine=None,
-               tile_shard=False):
+               tile_shard=False, cancel=None):
         """Returns (film (H+2b, W+2b, 5) float32, per-sample records or None, stats dict).
         engine: None (the library's default), 'wavefront', 'megakernel' or 'kdtree'
         (the wavefront engine tracing through the reference's kd-tree).
         row = (row_block, row_stride, row_phase); tile_shard: row_stride/row_phase
-        select 8x8 tiles (MTSGPU_FLAG_TILE_SHARD) instead of row blocks."""
+        select 8x8 tiles (MTSGPU_FLAG_TILE_SHARD) instead of row blocks.
+        cancel: a ctypes.c_int32 the library polls between launches (a non-zero word
+        ends the render with MTSGPU_ECANCEL); not passed on to a MultiChannelIntegrator."""
         if isinstance(integ, MultiChannelIntegrator):
             return self._render_multichannel(integ, window, samples, row, traversal_stats, engine, tile_shard)
         sc = self.scene
@@ -339,6 +345,8 @@ class Context:
         if tile_shard:
             p.flags |= abi.FLAG_TILE_SHARD
         p.flags |= self._engine_flags(engine)
+        if cancel is not None:
+            p.cancel = C.pointer(cancel)
         b = film_border(integ.rfilter, integ.rfilterParam)
         film = np.zeros((H + 2 * b, W + 2 * b, 5), np.float32)
         smp = np.zeros((w * h * integ.sampleCount, abi.SAMPLE_RECORD_FLOATS), np.float32) if samples else None
