@@ -440,6 +440,45 @@ int mtsgpu_develop_multi(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *par
 /* `films` is a host array of device pointers, `out_device` a device pointer. */
 int mtsgpu_develop_multi_device(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *params,
                                 const float *const *films, void *out_device, void *stream);
+/* ldrfilm develop (LDRFilm::develop, src/films/ldrfilm.cpp:300-321): the film
+ * interior, divided by its weights as mtsgpu_develop does, to 8-bit
+ * `pixel_format` (Bitmap::convert -> convertScalar, src/libcore/fmtconv.cpp:
+ * 955-1005, 1104-1111, 1137-1160).
+ *   MTSGPU_TONEMAP_GAMMA: value * powf(2, exposure), applyGamma(1/gamma) unless
+ *     gamma is 1 (gamma -1: the sRGB curve), min(255, max(0, v*255 + 0.5f)) cast
+ *     to uint8; alpha without multiplier and gamma.
+ *   MTSGPU_TONEMAP_REINHARD: the float32 conversion, Bitmap::tonemapReinhard
+ *     (src/libcore/bitmap.cpp:1711-1854: the sequential float sum of
+ *     fastlog(1e-3f + luminance) in row-major pixel order, the maximum luminance
+ *     with its reset at a luminance of exactly 1024, the operator per pixel; a
+ *     black image is left alone), then gamma and rounding as above with
+ *     multiplier 1; `exposure` is ignored.
+ * powf(2, exposure) and the tonemapper's scalars are computed on the device.
+ * Output: (film_height-2*border) rows of (film_width-2*border) pixels of 1-4
+ * bytes, channels interleaved.  `info2` may be NULL; otherwise it receives
+ * {logAvgLuminance, maxLuminance} as the reference logs them (ldrfilm.cpp:
+ * 312-316), zeros for the gamma method.  MTSGPU_EINVAL for an XYZ[A] pixel
+ * format (ldrfilm.cpp:159-170) or an unknown method. */
+enum { MTSGPU_TONEMAP_GAMMA = 0, MTSGPU_TONEMAP_REINHARD = 1 };
+typedef struct {
+    uint32_t film_width, film_height;   /* the rendered film incl. borders (W+2b, H+2b) */
+    uint32_t border;                    /* b                                             */
+    int32_t pixel_format;               /* MTSGPU_PIX_LUMINANCE .. MTSGPU_PIX_RGBA       */
+    int32_t tonemap_method;             /* MTSGPU_TONEMAP_*                              */
+    float gamma;                        /* 'gamma' (-1 = sRGB)                           */
+    float exposure;                     /* 'exposure', gamma method only                 */
+    float key, burn;                    /* 'key' (0.18), 'burn' (0), reinhard only       */
+} mtsgpu_develop_ldr_params;
+/* Host memory (film and out; staged through the context's buffers). */
+int mtsgpu_develop_ldr(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *params, const float *film, uint8_t *out,
+                       float info2[2]);
+/* `film_device` / `out_device` are device pointers, `out_device` aligned to the
+ * pixel size where that is 2 or 4 bytes (such a pixel is one store); `stream` a
+ * hipStream_t (NULL: the context's stream).  Returns after the stream is
+ * synchronised.  The reinhard method keeps its scratch (8 bytes per pixel) in
+ * the context, so one context develops one film at a time. */
+int mtsgpu_develop_ldr_device(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *params, const float *film_device,
+                              uint8_t *out_device, void *stream, float info2[2]);
 /* Host-only (no device needed): configure `scene` and return per BSDF the scalar
  * factor of its getDiffuseReflectance: plastic 1 - m_fdrExt (plastic.cpp:219-221),
  * roughplastic with a constant alpha m_externalRoughTransmittance->evalDiffuse(alpha)

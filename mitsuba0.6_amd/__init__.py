@@ -21,11 +21,11 @@ SOBOL_PARAMS = os.path.join(DATA_DIR, 'sobol_joe_kuo_1024.txt')
 from . import abi  # noqa: E402
 from .scene import (BSDF, DirectIntegrator, Emitter, FieldIntegrator, Mesh, MultiChannelIntegrator,  # noqa: E402
                     PathIntegrator, Scene, Sensor, VolpathIntegrator, film_border, look_at)
-from .film import HDRFilm, MFilm  # noqa: E402
+from .film import HDRFilm, LDRFilm, MFilm  # noqa: E402
 from .transform import Transform  # noqa: E402
 from .xmlscene import load_scene, save_scene  # noqa: E402
 
 __all__ = ['abi', 'BSDF', 'DirectIntegrator', 'Emitter', 'FieldIntegrator', 'Mesh', 'MultiChannelIntegrator',
-           'PathIntegrator', 'Scene', 'Sensor', 'VolpathIntegrator', 'HDRFilm', 'MFilm',
+           'PathIntegrator', 'Scene', 'Sensor', 'VolpathIntegrator', 'HDRFilm', 'LDRFilm', 'MFilm',
            'film_border', 'look_at', 'Transform', 'load_scene', 'save_scene', 'PKG_DIR', 'LIB_PATH',
            'SOBOL_PARAMS']

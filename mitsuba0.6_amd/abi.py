@@ -118,6 +118,16 @@ class DevelopMultiParams(C.Structure):
                 ('component_format', C.c_int32)]
 
 
+TONEMAP_GAMMA, TONEMAP_REINHARD = 0, 1
+
+
+class DevelopLdrParams(C.Structure):
+    """mtsgpu_develop_ldr_params (include/mtsgpu.h)."""
+    _fields_ = [('film_width', C.c_uint32), ('film_height', C.c_uint32), ('border', C.c_uint32),
+                ('pixel_format', C.c_int32), ('tonemap_method', C.c_int32), ('gamma', C.c_float),
+                ('exposure', C.c_float), ('key', C.c_float), ('burn', C.c_float)]
+
+
 class Stats(C.Structure):
     _fields_ = [('samples', C.c_uint64), ('rays', C.c_uint64), ('shadow_rays', C.c_uint64),
                 ('path_length_sum', C.c_uint64), ('node_visits', C.c_uint64),

@@ -58,6 +58,11 @@ hipError_t mtsg_launch_sfmt_probe(uint32_t *w, unsigned long long *out, int n, h
 hipError_t mtsg_launch_develop(const mtsgpu_develop_params &P, const float *film, void *out, int num_cus,
                                hipStream_t s);
 int mtsg_develop_channels(int pixel_format);
+// ldrfilm develop (ldrfilm_kernel.hip)
+hipError_t mtsg_launch_develop_ldr(const mtsgpu_develop_ldr_params &P, const float *film, uint8_t *out, void *scratch,
+                                   int num_cus, hipStream_t s);
+size_t mtsg_develop_ldr_scratch(const mtsgpu_develop_ldr_params &P);
+size_t mtsg_develop_ldr_info_offset();
 
 namespace {
 
@@ -102,6 +107,7 @@ struct mtsgpu_ctx {
     DevBuf qrays, qhits;      // mtsgpu_trace_rays staging
     DevBuf film_own, film_spill, samples, counters, contrib;
     DevBuf dev_in, dev_out;   // staging of mtsgpu_develop (host film -> developed image)
+    DevBuf ldr_scratch;       // mtsgpu_develop_ldr, reinhard: log-luminance terms, luminances, the tonemapper's scalars
     DevBuf field_first;       // the field pass: first global primitive of each shape (MtsgFieldArgs::shape_first)
     std::vector<uint32_t> field_first_host;   // kept alive for the async upload
     // wavefront pipeline: path slots, ray queues and results, counters
@@ -1262,6 +1268,78 @@ int mtsgpu_develop_multi(mtsgpu_ctx *ctx, const mtsgpu_develop_multi_params *P, 
     return MTSGPU_OK;
 }
 
+// ldrfilm develop (ldrfilm_kernel.hip): LDRFilm::develop (src/films/ldrfilm.cpp:300-321) ->
+// Bitmap::convert to uint8 (src/libcore/fmtconv.cpp:955-1005, 1104-1111, 1137-1160) and, for the
+// reinhard method, Bitmap::tonemapReinhard (src/libcore/bitmap.cpp:1711-1854)
+namespace {
+int develop_ldr_check(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *P, const void *out, size_t *out_bytes) {
+    if (!ctx) return MTSGPU_EINVAL;
+    if (!P) return fail(ctx, MTSGPU_EINVAL, "develop params are NULL");
+    if (P->pixel_format < MTSGPU_PIX_LUMINANCE || P->pixel_format > MTSGPU_PIX_RGBA)   // ldrfilm.cpp:159-170
+        return fail(ctx, MTSGPU_EINVAL, "develop_ldr: the pixel format must be luminance, luminanceAlpha, rgb or rgba");
+    if (P->tonemap_method != MTSGPU_TONEMAP_GAMMA && P->tonemap_method != MTSGPU_TONEMAP_REINHARD)
+        return fail(ctx, MTSGPU_EINVAL, "develop_ldr: unknown tonemap method");
+    if (P->film_width <= 2 * P->border || P->film_height <= 2 * P->border)
+        return fail(ctx, MTSGPU_EINVAL, "develop: film smaller than its borders");
+    const size_t ch = (size_t)mtsg_develop_channels(P->pixel_format);
+    // a pixel of 2 or 4 bytes is written by one store
+    if (out && (ch == 2 || ch == 4) && (uintptr_t)out % ch != 0)
+        return fail(ctx, MTSGPU_EINVAL, "develop_ldr: output not aligned to its pixel size");
+    *out_bytes = (size_t)(P->film_width - 2 * P->border) * (P->film_height - 2 * P->border) * ch;
+    return MTSGPU_OK;
+}
+
+// launch on `s`, wait, and hand back {logAvgLuminance, maxLuminance}
+int develop_ldr_run(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *P, const float *film_device,
+                    uint8_t *out_device, uint8_t *out_host, size_t ob, hipStream_t s, float info2[2]) {
+    hipError_t e;
+    const size_t sb = mtsg_develop_ldr_scratch(*P);
+    if (sb && (e = ctx->ldr_scratch.ensure(sb)) != hipSuccess) return hip_fail(ctx, e, "develop buffers");
+    float info[2] = {0.0f, 0.0f};
+    if ((e = mtsg_launch_develop_ldr(*P, film_device, out_device, sb ? ctx->ldr_scratch.p : nullptr, ctx->num_cus,
+                                     s)) != hipSuccess ||
+        (out_host && (e = hipMemcpyAsync(out_host, out_device, ob, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
+        (sb && info2 &&
+         (e = hipMemcpyAsync(info, (const char *)ctx->ldr_scratch.p + mtsg_develop_ldr_info_offset(), sizeof(info),
+                             hipMemcpyDeviceToHost, s)) != hipSuccess) ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+        return hip_fail(ctx, e, "develop_ldr");
+    if (info2) {
+        info2[0] = info[0];
+        info2[1] = info[1];
+    }
+    return MTSGPU_OK;
+}
+}  // namespace
+
+int mtsgpu_develop_ldr_device(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *P, const float *film_device,
+                              uint8_t *out_device, void *stream, float info2[2]) {
+    size_t ob = 0;
+    const int rc = develop_ldr_check(ctx, P, out_device, &ob);
+    if (rc != MTSGPU_OK) return rc;
+    if (!film_device || !out_device) return fail(ctx, MTSGPU_EINVAL, "develop: NULL buffer");
+    (void)hipSetDevice(ctx->device);
+    return develop_ldr_run(ctx, P, film_device, out_device, nullptr, ob, stream ? (hipStream_t)stream : ctx->stream,
+                           info2);
+}
+
+int mtsgpu_develop_ldr(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *P, const float *film, uint8_t *out,
+                       float info2[2]) {
+    size_t ob = 0;
+    const int rc = develop_ldr_check(ctx, P, nullptr, &ob);
+    if (rc != MTSGPU_OK) return rc;
+    if (!film || !out) return fail(ctx, MTSGPU_EINVAL, "develop: NULL buffer");
+    (void)hipSetDevice(ctx->device);
+    const size_t ib = (size_t)P->film_width * P->film_height * 5 * sizeof(float);
+    hipError_t e;
+    if ((e = ctx->dev_in.ensure(ib)) != hipSuccess || (e = ctx->dev_out.ensure(ob)) != hipSuccess)
+        return hip_fail(ctx, e, "develop buffers");
+    hipStream_t s = ctx->stream;
+    if ((e = hipMemcpyAsync(ctx->dev_in.p, film, ib, hipMemcpyHostToDevice, s)) != hipSuccess)
+        return hip_fail(ctx, e, "develop_ldr");
+    return develop_ldr_run(ctx, P, (const float *)ctx->dev_in.p, (uint8_t *)ctx->dev_out.p, out, ob, s, info2);
+}
+
 int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, char *msg, size_t cap) {
     if (!scene || !factors) return MTSGPU_EINVAL;
     HostScene H;
@@ -1290,7 +1368,7 @@ void mtsgpu_destroy(mtsgpu_ctx *ctx) {
                       &ctx->film_own, &ctx->film_spill, &ctx->samples, &ctx->counters, &ctx->contrib,
                       &ctx->env, &ctx->env_texels, &ctx->env_rows, &ctx->env_cols, &ctx->env_weights, &ctx->env_grows, &ctx->env_gcols,
                       &ctx->rtrans, &ctx->texcoords, &ctx->qrays, &ctx->qhits, &ctx->field_first,
-                      &ctx->dev_in, &ctx->dev_out, &ctx->wf_state, &ctx->wf_ray, &ctx->wf_rslot, &ctx->wf_cls,
+                      &ctx->dev_in, &ctx->dev_out, &ctx->ldr_scratch, &ctx->wf_state, &ctx->wf_ray, &ctx->wf_rslot, &ctx->wf_cls,
                       &ctx->wf_cnt, &ctx->wf_hit, &ctx->wf_hitrec, &ctx->wf_occl, &ctx->wf_live, &ctx->wf_ovf, &ctx->wf_part, &ctx->wf_kind, &ctx->rp_order, &ctx->rp_start, &ctx->rp_sfmt, &ctx->env_grows, &ctx->env_gcols};
     for (DevBuf *b : bufs) b->release();
     for (hipEvent_t &e : ctx->wf_ev)

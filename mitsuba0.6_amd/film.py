@@ -1,5 +1,13 @@
-"""`hdrfilm` and `mfilm`: film output of the GPU path -- develop + OpenEXR /
-PFM / RGBE files (hdrfilm), MATLAB / Mathematica text or NumPy `.npy` (mfilm).
+"""`hdrfilm`, `mfilm` and `ldrfilm`: film output of the GPU path -- develop +
+OpenEXR / PFM / RGBE files (hdrfilm), MATLAB / Mathematica text or NumPy `.npy`
+(mfilm), tonemapped 8-bit PNG (ldrfilm).
+
+LDRFilm mirrors src/films/ldrfilm.cpp:130-196, 300-359: its properties, defaults
+and errors; `develop()` runs `mtsgpu_develop_ldr` on the device (exposure /
+gamma, or Reinhard's operator with its ordered log-luminance sum) and returns
+uint8; `write_png` / `read_png` follow Bitmap::writePNG (bitmap.cpp:2590-2650)
+with zlib alone.  JPEG output is not implemented, and PNG is an output format
+only (`load_bitmap` does not read it).
 
 Mirrors HDRFilm (src/films/hdrfilm.cpp:205-360, 481-535):
 - The property names, defaults and errors of the constructor (raised as
@@ -246,6 +254,104 @@ class MFilm:
         return path
 
 
+LDR_PIXEL_FORMATS = ('luminance', 'luminancealpha', 'rgb', 'rgba')
+LDR_EXTENSIONS = {'png': '.png', 'jpeg': '.jpg'}
+
+
+@dataclass
+class LDRFilm:
+    """The `ldrfilm` plugin (src/films/ldrfilm.cpp:130-196, 300-359): 8-bit output,
+    developed on the device by `mtsgpu_develop_ldr` -- the weight division, then
+    either exposure and gamma (`tonemapMethod` "gamma") or Reinhard's operator and
+    gamma ("reinhard": Bitmap::tonemapReinhard, bitmap.cpp:1711-1854), then rounding
+    to uint8 (fmtconv.cpp:1137-1160).  `gamma` -1 is the sRGB curve.
+
+    PNG files are written here; JPEG is accepted by the constructor as the
+    reference accepts it (an alpha channel is dropped, ldrfilm.cpp:172-178), but
+    `write` raises NotImplementedError: there is no JPEG encoder in this package.
+    The film size, crop window and reconstruction filter live on Sensor /
+    PathIntegrator; the defaults are hdrfilm's (768x576, gaussian)."""
+    fileFormat: str = 'png'
+    pixelFormat: str = 'rgb'
+    tonemapMethod: str = 'gamma'
+    gamma: float = -1.0
+    exposure: float = 0.0
+    key: float = 0.18
+    burn: float = 0.0
+    banner: bool = True
+
+    def __post_init__(self):
+        ff = self.fileFormat.lower()
+        if ff == 'png':
+            self.fileFormat = 'png'
+        elif ff in ('jpg', 'jpeg'):
+            self.fileFormat = 'jpeg'
+        else:
+            raise ValueError('The "fileFormat" parameter must either be equal to "png" or "jpeg"!')
+        self.tonemapMethod = self.tonemapMethod.lower()
+        if self.tonemapMethod not in ('gamma', 'reinhard'):
+            raise ValueError('The "method" parameter must either be equal to "gamma" or "reinhard"!')
+        fmt = self.pixelFormat.lower()
+        if fmt not in LDR_PIXEL_FORMATS:
+            raise ValueError('The "pixelFormat" parameter must either be equal to "luminance", "luminanceAlpha", '
+                             '"rgb", or "rgba"!')
+        if self.fileFormat == 'jpeg' and fmt in ('luminancealpha', 'rgba'):     # ldrfilm.cpp:172-178
+            warnings.warn('Ignoring request to write an alpha channel, since the JPEG format does not support it.')
+            fmt = 'luminance' if fmt == 'luminancealpha' else 'rgb'
+        self._fmt = fmt
+        self.gamma, self.exposure = float(f32(self.gamma)), float(f32(self.exposure))
+        self.key, self.burn = float(f32(self.key)), float(f32(self.burn))
+        self.componentFormat = 'uint8'
+
+    @property
+    def pixel_format(self):
+        """The effective pixel format (after JPEG's alpha override)."""
+        return self._fmt
+
+    @property
+    def channel_names(self):
+        return list(PIXEL_FORMATS[self._fmt][1])
+
+    @property
+    def hasAlpha(self):
+        """LDRFilm::hasAlpha (ldrfilm.cpp:355-359)."""
+        return self._fmt in ('luminancealpha', 'rgba')
+
+    def develop_params(self, film_shape, border):
+        p = abi.DevelopLdrParams()
+        p.film_height, p.film_width = int(film_shape[0]), int(film_shape[1])
+        p.border = int(border)
+        p.pixel_format = PIXEL_FORMATS[self._fmt][0]
+        p.tonemap_method = abi.TONEMAP_REINHARD if self.tonemapMethod == 'reinhard' else abi.TONEMAP_GAMMA
+        p.gamma, p.exposure, p.key, p.burn = self.gamma, self.exposure, self.key, self.burn
+        return p
+
+    def output_array(self, film_shape, border):
+        h, w = film_shape[0] - 2 * border, film_shape[1] - 2 * border
+        return np.empty((h, w, len(self.channel_names)), np.uint8)
+
+    def develop(self, ctx, film, border):
+        """LDRFilm::develop's conversion on the device (ldrfilm.cpp:306-321): `film` is the
+        (H+2b, W+2b, 5) float32 film mtsgpu_render returned; returns (H, W, C) uint8."""
+        if self.banner:
+            _warn_banner('ldrfilm')
+        return ctx.develop_ldr(film, border, self)
+
+    def output_path(self, dest):
+        """The destination with the proper extension (ldrfilm.cpp:335-345)."""
+        root, ext = os.path.splitext(str(dest))
+        proper = LDR_EXTENSIONS[self.fileFormat]
+        return str(dest) if ext.lower() == proper else root + proper
+
+    def write(self, dest, image):
+        """Bitmap::write(EPNG) of the developed image to `dest` (extension fixed as the reference does)."""
+        if self.fileFormat != 'png':
+            raise NotImplementedError('ldrfilm fileFormat="jpeg": this package has no JPEG encoder (use "png")')
+        path = self.output_path(dest)
+        write_png(path, image, self.gamma)
+        return path
+
+
 def _fmt_g(x, digits):
     """`os << std::setprecision(digits) << float` (libstdc++: printf "%.*g" of the value as double)."""
     x = float(x)
@@ -307,11 +413,11 @@ def write_npy(path, img):
 _banner_warned = False
 
 
-def _warn_banner():
+def _warn_banner(plugin='hdrfilm'):
     global _banner_warned
     if not _banner_warned:
-        warnings.warn('hdrfilm banner=true: the Mitsuba logo overlay is not drawn (set banner=false for '
-                      'pixel-identical output)')
+        warnings.warn('%s banner=true: the Mitsuba logo overlay is not drawn (set banner=false for '
+                      'pixel-identical output)' % plugin)
         _banner_warned = True
 
 
@@ -502,6 +608,123 @@ def read_rgbe(path):
                     p += 1 + k
                 x += k
     return rgbe_to_float(out)
+
+
+# ---------------------------------------------------------------------------
+# PNG (Bitmap::writePNG, 8 bits per component)
+# ---------------------------------------------------------------------------
+PNG_MAGIC = b'\x89PNG\r\n\x1a\n'
+_PNG_COLOR = {1: 0, 2: 4, 3: 2, 4: 6}      # channels -> colour type (grey, grey+alpha, RGB, RGBA)
+_PNG_CHANNELS = {v: k for k, v in _PNG_COLOR.items()}
+
+
+def _png_chunk(tag, data):
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def write_png(path, img, gamma=-1.0):
+    """Bitmap::writePNG (bitmap.cpp:2590-2650) of an (H, W[, C]) uint8 image: 8-bit
+    greyscale, grey+alpha, RGB or RGBA, not interlaced.  Colour chunks as libpng
+    writes them ahead of the image: for gamma -1 what png_set_sRGB_gAMA_and_cHRM
+    (intent ABSOLUTE) sets -- gAMA 45455, sRGB, cHRM of the sRGB primaries -- in
+    libpng's order, otherwise a gAMA chunk of 1/gamma.  No text chunks (the
+    metadata and annotations are not reproduced); filter type 0 on every row."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8:
+        raise ValueError('writePNG(): component format must be EUInt8!')
+    if img.ndim == 2:
+        img = img[:, :, None]
+    if img.ndim != 3 or img.shape[2] not in _PNG_COLOR:
+        raise ValueError('writePNG(): Unsupported bitmap type!')
+    h, w, c = img.shape
+    out = [PNG_MAGIC, _png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, _PNG_COLOR[c], 0, 0, 0))]
+    gamma = float(f32(gamma))
+    if gamma == -1:
+        out.append(_png_chunk(b'gAMA', struct.pack('>I', 45455)))
+        out.append(_png_chunk(b'sRGB', b'\x03'))
+        out.append(_png_chunk(b'cHRM', struct.pack('>8I', 31270, 32900, 64000, 33000, 30000, 60000, 15000, 6000)))
+    elif gamma > 0 and np.isfinite(gamma):
+        # png_set_gAMA(1 / m_gamma): the float quotient as a 1e5 fixed-point number, rounded
+        out.append(_png_chunk(b'gAMA', struct.pack('>I', int(np.floor(float(f32(1) / f32(gamma)) * 100000.0 + 0.5)))))
+    rows = np.zeros((h, 1 + w * c), np.uint8)
+    rows[:, 1:] = img.reshape(h, w * c)
+    out.append(_png_chunk(b'IDAT', zlib.compress(rows.tobytes())))
+    out.append(_png_chunk(b'IEND', b''))
+    with open(path, 'wb') as fh:
+        fh.write(b''.join(out))
+
+
+def _png_unfilter(raw, h, stride, bpp):
+    """The five filter types of the PNG specification, row by row."""
+    out = np.zeros((h, stride), np.uint8)
+    prev = np.zeros(stride, np.int32)
+    pos = 0
+    for y in range(h):
+        ft = raw[pos]
+        line = np.frombuffer(raw, np.uint8, stride, pos + 1).astype(np.int32)
+        pos += 1 + stride
+        if ft == 0:
+            cur = line
+        elif ft == 2:
+            cur = (line + prev) & 0xFF
+        elif ft in (1, 3, 4):
+            cur = np.zeros(stride, np.int32)
+            for x in range(stride):
+                a = cur[x - bpp] if x >= bpp else 0
+                b = prev[x]
+                if ft == 1:
+                    p = a
+                elif ft == 3:
+                    p = (a + b) >> 1
+                else:
+                    cc = prev[x - bpp] if x >= bpp else 0
+                    pa, pb, pc = abs(b - cc), abs(a - cc), abs(a + b - 2 * cc)
+                    p = a if pa <= pb and pa <= pc else (b if pb <= pc else cc)
+                cur[x] = (line[x] + p) & 0xFF
+        else:
+            raise ValueError('readPNG(): unknown filter type %d' % ft)
+        out[y] = cur
+        prev = cur
+    return out
+
+
+def read_png(path):
+    """An 8-bit, non-interlaced PNG (greyscale, grey+alpha, RGB or RGBA) ->
+    ((H, W, C) uint8, gamma): gamma is -1 for a file with an sRGB chunk, 1 / gAMA
+    for one with a gAMA chunk only, None without either.  Every chunk's CRC is checked."""
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    if data[:8] != PNG_MAGIC:
+        raise ValueError('readPNG(): not a PNG file')
+    pos, idat, hdr, srgb, gama = 8, [], None, False, None
+    while pos < len(data):
+        n, tag = struct.unpack_from('>I4s', data, pos)
+        body = data[pos + 8:pos + 8 + n]
+        if struct.unpack_from('>I', data, pos + 8 + n)[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
+            raise ValueError('readPNG(): bad CRC in chunk %r' % tag)
+        pos += 12 + n
+        if tag == b'IHDR':
+            hdr = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+        elif tag == b'sRGB':
+            srgb = True
+        elif tag == b'gAMA':
+            gama = struct.unpack('>I', body)[0]
+        elif tag == b'IEND':
+            break
+    if hdr is None:
+        raise ValueError('readPNG(): no IHDR chunk')
+    w, h, depth, color, _, _, interlace = hdr
+    if depth != 8 or color not in _PNG_CHANNELS or interlace != 0:
+        raise NotImplementedError('readPNG(): only 8-bit non-interlaced grey / grey+alpha / RGB / RGBA files')
+    c = _PNG_CHANNELS[color]
+    raw = zlib.decompress(b''.join(idat))
+    if len(raw) != h * (1 + w * c):
+        raise ValueError('readPNG(): wrong amount of image data')
+    img = _png_unfilter(raw, h, w * c, c).reshape(h, w, c)
+    gamma = -1.0 if srgb else (float(f32(1) / f32(gama / 100000.0)) if gama else None)
+    return img, gamma
 
 
 # ---------------------------------------------------------------------------

@@ -34,7 +34,8 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
            'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
            'mtsgpu_face_normals_host', 'mtsgpu_render_fields', 'mtsgpu_render_fields_device', 'mtsgpu_develop_multi',
-           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host']
+           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_develop_ldr',
+           'mtsgpu_develop_ldr_device']
 
 _lib = None
 
@@ -104,6 +105,10 @@ def load_library(path=None):
         L.mtsgpu_develop_multi_device.argtypes = [C.c_void_p, P(abi.DevelopMultiParams), P(C.c_void_p), C.c_void_p,
                                                   C.c_void_p]
         L.mtsgpu_albedo_factors_host.argtypes = [P(abi.SceneDesc), P(C.c_float), C.c_char_p, C.c_size_t]
+    if hasattr(L, 'mtsgpu_develop_ldr'):   # added within ABI 8 as well (ldrfilm)
+        L.mtsgpu_develop_ldr.argtypes = [C.c_void_p, P(abi.DevelopLdrParams), P(C.c_float), C.c_void_p, P(C.c_float)]
+        L.mtsgpu_develop_ldr_device.argtypes = [C.c_void_p, P(abi.DevelopLdrParams), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, P(C.c_float)]
     L.mtsgpu_group_create.argtypes = [P(C.c_int), C.c_int, P(C.c_void_p)]
     L.mtsgpu_group_size.argtypes = [C.c_void_p]
     L.mtsgpu_group_upload_scene.argtypes = [C.c_void_p, P(abi.SceneDesc)]
@@ -451,6 +456,31 @@ class Context:
         p = hdrfilm.develop_params(film_shape, border)
         self._check(self.L.mtsgpu_develop_device(self.h, C.byref(p), C.c_void_p(film_ptr), C.c_void_p(out_ptr),
                                                   C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def develop_ldr(self, film, border, ldrfilm, info=False):
+        """ldrfilm develop on the device (mtsgpu_develop_ldr): `film` (H+2b, W+2b, 5)
+        float32 host array -> (H, W, C) uint8; with info=True also the float32 pair
+        {logAvgLuminance, maxLuminance} of the reinhard method (zeros for gamma)."""
+        film = np.ascontiguousarray(film, np.float32)
+        if film.ndim != 3 or film.shape[2] != 5:
+            raise ValueError('develop_ldr: film must be (H+2b, W+2b, 5) float32')
+        p = ldrfilm.develop_params(film.shape, border)
+        out = ldrfilm.output_array(film.shape, border)
+        info2 = np.zeros(2, np.float32)
+        self._check(self.L.mtsgpu_develop_ldr(self.h, C.byref(p), abi.fptr(film), out.ctypes.data_as(C.c_void_p),
+                                              abi.fptr(info2)))
+        return (out, info2) if info else out
+
+    def develop_ldr_device(self, film_ptr, film_shape, border, ldrfilm, out_ptr, stream_ptr=None):
+        """Same on device buffers (e.g. torch tensors' data_ptr()); the output holds
+        ldrfilm.output_array(film_shape, border).nbytes bytes and is aligned to its pixel
+        size.  Returns the float32 pair {logAvgLuminance, maxLuminance}."""
+        p = ldrfilm.develop_params(film_shape, border)
+        info2 = np.zeros(2, np.float32)
+        self._check(self.L.mtsgpu_develop_ldr_device(self.h, C.byref(p), C.c_void_p(film_ptr), C.c_void_p(out_ptr),
+                                                     C.c_void_p(stream_ptr) if stream_ptr else None,
+                                                     abi.fptr(info2)))
+        return info2
 
     def kdtree(self):
         """The reference's SAH kd-tree of the uploaded scene (mtsgpu_debug_kdtree):

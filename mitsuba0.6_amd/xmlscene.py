@@ -19,8 +19,9 @@ Plugins:
   most one of `path` / `volpath` / `direct`.
 - sensor `perspective` (fov/fovAxis or focalLength, near/farClip, toWorld),
   with sampler `sobol` (sampleCount, scramble) or `independent` (sampleCount;
-  the default without a <sampler>), film `hdrfilm` or `mfilm` (size, crop
-  window, pixel/file formats), whose rfilter is `box` or `gaussian`.
+  the default without a <sampler>), film `hdrfilm`, `mfilm` or `ldrfilm` (size,
+  crop window, pixel/file formats; ldrfilm's tonemapMethod, gamma, exposure, key
+  and burn), whose rfilter is `box` or `gaussian`.
 - shapes `obj`, `ply`, `serialized`, `cube` (triangle meshes) and the analytic
   `rectangle`, `disk`, `sphere`.
 - BSDFs `diffuse`, `roughconductor`, `roughdielectric`, `roughplastic`,
@@ -37,7 +38,7 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from .film import HDRFilm, MFilm, load_bitmap, read_pfm, write_pfm  # noqa: F401  (Bitmap readers/writers)
+from .film import HDRFilm, LDRFilm, MFilm, load_bitmap, read_pfm, write_pfm  # noqa: F401  (Bitmap readers/writers)
 from .obj import load_obj, srgb_to_linear, strtof
 from .ply import load_ply
 from .scene import (BSDF, Checkerboard, DirectIntegrator, Emitter, FieldIntegrator, Mesh, MultiChannelIntegrator,
@@ -512,8 +513,8 @@ class XMLSceneLoader:
         width, height = 768, 576
         rfilter, rparam, has_alpha, crop, hdr = 'gaussian', 0.5, False, None, HDRFilm()
         if film is not None:
-            if film.plugin not in ('hdrfilm', 'mfilm'):
-                raise NotImplementedError('film "%s" (hdrfilm, mfilm)' % film.plugin)
+            if film.plugin not in ('hdrfilm', 'mfilm', 'ldrfilm'):
+                raise NotImplementedError('film "%s" (hdrfilm, mfilm, ldrfilm)' % film.plugin)
             mf = film.plugin == 'mfilm'
             width, height = film.get('width', 1 if mf else 768), film.get('height', 1 if mf else 576)   # film.cpp:27-33
             try:
@@ -522,6 +523,11 @@ class XMLSceneLoader:
                                                                                                    'luminance'),
                                 digits=film.get('digits', 4), variable=film.get('variable', 'data'))
                     rfilter, rparam = 'box', 0.5            # mfilm.cpp:156-165: box by default
+                elif film.plugin == 'ldrfilm':              # ldrfilm.cpp:130-183
+                    hdr = LDRFilm(fileFormat=film.get('fileFormat', 'png'), pixelFormat=film.get('pixelFormat', 'rgb'),
+                                  tonemapMethod=film.get('tonemapMethod', 'gamma'), gamma=film.get('gamma', -1.0),
+                                  exposure=film.get('exposure', 0.0), key=film.get('key', 0.18),
+                                  burn=film.get('burn', 0.0), banner=film.get('banner', True))
                 else:
                     hdr = HDRFilm(fileFormat=film.get('fileFormat', 'openexr'),
                                   pixelFormat=film.get('pixelFormat', 'rgb'),
@@ -755,10 +761,10 @@ def save_scene(scene, integ, directory, name='scene.xml'):
         L.append('    <sampler type="sobol"><integer name="sampleCount" value="%d"/>'
                  '<integer name="scramble" value="%d"/></sampler>' % (integ.sampleCount, integ.scramble))
     hf = integ.film or HDRFilm()
-    mf = isinstance(hf, MFilm)
-    L.append('    <film type="%s">' % ('mfilm' if mf else 'hdrfilm'))
+    mf, lf = isinstance(hf, MFilm), isinstance(hf, LDRFilm)
+    L.append('    <film type="%s">' % ('mfilm' if mf else 'ldrfilm' if lf else 'hdrfilm'))
     L.append('      <integer name="width" value="%d"/><integer name="height" value="%d"/>' % (s.width, s.height))
-    multi = not mf and len(hf.pixel_formats) != 1
+    multi = not mf and not lf and len(hf.pixel_formats) != 1
     if multi:       # one pixel format and channel-name prefix per nested integrator (hdrfilm.cpp:243-292)
         fmt = ', '.join(hf.pixel_formats)
         L.append('      <string name="channelNames" value="%s"/>' % hf.channelNames)
@@ -768,6 +774,13 @@ def save_scene(scene, integ, directory, name='scene.xml'):
     if mf:
         L.append('      <string name="fileFormat" value="%s"/><integer name="digits" value="%d"/>'
                  '<string name="variable" value="%s"/>' % (hf.fileFormat, hf.digits, hf.variable))
+    elif lf:
+        L.append('      <string name="fileFormat" value="%s"/><string name="tonemapMethod" value="%s"/>'
+                 % (hf.fileFormat, hf.tonemapMethod))
+        L.append('      <float name="gamma" value="%s"/><float name="exposure" value="%s"/>'
+                 '<float name="key" value="%s"/><float name="burn" value="%s"/>'
+                 % (_fmt(hf.gamma), _fmt(hf.exposure), _fmt(hf.key), _fmt(hf.burn)))
+        L.append('      <boolean name="banner" value="%s"/>' % str(bool(hf.banner)).lower())
     else:
         L.append('      <string name="fileFormat" value="%s"/><string name="componentFormat" value="%s"/>'
                  % (hf.fileFormat, hf.componentFormat))
