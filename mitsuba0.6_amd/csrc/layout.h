@@ -333,8 +333,9 @@ struct MtsgLaunch {
                                       // gather mode two, one 32 B sector: {L.rgb, sx (alpha in its sign)},
                                       // {sy (negative: an invalid sample), 0, 0, 0}
     float *film_own;                  // fw*fh*5: own-pixel sums (ordered reduction), or the gathered film
-    double *film_spill;               // fw*fh*5: splats into other pixels (box filter only), double atomics:
-                                      // a pixel's few neighbour splats sum exactly, in any order (dpath.h film_splat)
+    double *film_spill;               // fw*fh*5: splats into other pixels (every filter outside gather mode), double
+                                      // atomics: a pixel's neighbour splats sum exactly, in any order, while
+                                      // sum|c| < 2^(q + 53) (dpath.h film_splat); wide gaussians leave that regime
     // gather mode (filters whose footprint covers neighbours, e.g. gaussian): the kernels store
     // each sample's value and position; film_gather<H> forms every pixel's sum in a fixed order
     uint32_t gather;                  // 1: gather mode

@@ -1,6 +1,12 @@
 """Box-filter neighbour splats (the spill film) sum in double on both sides
 (dpath.h film_splat, oracle film_put), so a pixel's spill total does not depend
-on the order its contributions land: float atomics made it schedule-dependent
+on the order its contributions land -- as long as every partial sum is exact,
+which holds when sum|c| < 2^(q + 53) for q the smallest exponent of a lowest
+set mantissa bit among the contributions (tests/film_ref.py certifies it per
+film value).  The box films of the suite do; a gaussian wide enough to take this path
+(H > 4: 121 and more pixels per footprint) leaves the regime in about a sixth
+of its film pixels, and tests/test_gpu_filter_widths.py compares those within
+a derived bound instead.  Float atomics made the total schedule-dependent
 once three or more samples splat into one pixel (one pixel of C3 at 1/4 rows
 changed with the megakernel's sample-run length, profiles/r06_rounds/).
 
