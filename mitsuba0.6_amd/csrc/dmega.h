@@ -48,7 +48,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     constexpr bool STATS = INSTR;
     constexpr bool ANA = (FEAT & MTSG_FEAT_ANA) != 0;
     constexpr bool HNODES = (FEAT & (MTSG_FEAT_GGX | MTSG_FEAT_NORD | MTSG_FEAT_NORC)) != 0;
-    extern __shared__ uint32_t lds[];
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     (void)stage_lds<SCENE_LDS>(L, lds);
     PathCounters c = {};   // INSTR statistics only: the always-on counts are wave-uniform (wc)
     WaveCounters wc = {};
@@ -122,18 +122,19 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
             // leave the same point, P.its.p
             float minS = INFINITY, maxS = -INFINITY, minC = INFINITY, maxC = -INFINITY;
             bool okS = false, okC = false;
+            f3 rcpS = mk(0, 0, 0), rcpC = mk(0, 0, 0);   // the clips' 1 / d, which scan_pair divides by
             wc.shadow += wave_count(st.active && st.haveShadow);
             wc.rays += wave_count(st.active && st.haveRay);
             if (st.active && st.haveShadow) {
-                if (!is_zero(st.P.neeC)) okS = ray_interval(S, st.P.its.p, st.sd, D_EPSILON, st.smaxt, true, minS, maxS);
+                if (!is_zero(st.P.neeC)) okS = ray_interval(S, st.P.its.p, st.sd, D_EPSILON, st.smaxt, true, minS, maxS, rcpS);
                 if (!okS) { minS = INFINITY; maxS = -INFINITY; }
             }
             if (st.active && st.haveRay) {
-                okC = ray_interval(S, st.P.its.p, st.rd, st.rmint, st.rmaxt, false, minC, maxC);
+                okC = ray_interval(S, st.P.its.p, st.rd, st.rmint, st.rmaxt, false, minC, maxC, rcpC);
                 if (!okC) { minC = INFINITY; maxC = -INFINITY; }
             }
             if (__any(okS || okC))
-                scan_pair<STATS>(L, st.P.its.p, st.sd, st.rd, minS, maxS, minC, maxC, occluded, hit,
+                scan_pair<STATS>(L, st.P.its.p, st.sd, st.rd, rcpS, rcpC, minS, maxS, minC, maxC, occluded, hit,
                                  prim, hu, hv, ht, c.tests);
             hit = hit && okC;
             occluded = occluded && okS;

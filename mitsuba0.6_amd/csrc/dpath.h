@@ -93,6 +93,11 @@ struct SobolCtx {
     uint32_t lds_dims, nibbles, scramble;
     bool indep;               // the `independent` sampler: `index` is a stream key
     bool replay;              // SFMT replay: draws come from the lane's SFMT stream
+    bool tight;               // a constant of the kernel (lds_view: SCENE_LDS): the LDS tables are read
+                              // through sobol_row, next2d's two dimensions together.  Taken by the
+                              // small-scene kernels, which are VALU-bound and where it was measured
+                              // (DESIGN.md 4, round 9); the large-scene kernels wait on memory and
+                              // keep the draws as they were
     uint32_t *sfmt;           // the streams (lane u: sfmt + u * MTSG_SFMT_WORDS)
 };
 
@@ -120,19 +125,100 @@ __device__ __forceinline__ float indep_float(uint64_t key, uint32_t dim) {
     return __uint_as_float((u >> 9) | 0x3f800000u) - 1.0f;
 }
 
-__device__ __forceinline__ float sobol_sample(const SobolCtx &C, uint64_t index, uint32_t dim) {
-    if (C.indep) return indep_float(index, dim);
-    uint32_t bits;
-    if (dim < C.lds_dims) {
-        lds_u32 *t = C.lds + dim * C.nibbles * 16;
-        bits = (C.nibbles == 8) ? sobol_bits<8>(t, index) : sobol_bits<MTSG_NIBBLES>(t, index);
-    } else {
-        glb_u32 *t = C.glob + (size_t)dim * MTSG_NIBBLES * 16;
-        bits = (C.nibbles == 8) ? sobol_bits<8>(t, index) : sobol_bits<MTSG_NIBBLES>(t, index);
+// The LDS tables' addressing.  A table starts at a multiple of 64 bytes (the kernels
+// declare `lds` 64-byte aligned; a dimension's table is nibbles * 64 bytes), so nibble c's
+// byte offset within a row, (index >> (4c - 2)) & 0x3c, does not carry into the base: one
+// shift and one v_and_or_b32 per nibble, the row (c * 16 words) in the read's offset field.
+// Written as an integer sum: still the right address wherever the base is not so aligned.
+template <int C>
+__device__ __forceinline__ lds_u32 *sobol_row(lds_u32 *tab, uint64_t index) {
+    const uint32_t w = C < 8 ? (uint32_t)index : (uint32_t)(index >> 32);
+    const uint32_t o = (C & 7) == 0 ? (w << 2) & 0x3cu : (w >> (4 * (C & 7) - 2)) & 0x3cu;
+    return (lds_u32 *)(uintptr_t)((uint32_t)(uintptr_t)tab + o);
+}
+// XOR of NIB table words (and `r`), folded three inputs at a time
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);   // the truth table of a ^ b ^ c
+#else
+    return a ^ b ^ c;
+#endif
+}
+template <int NIB>
+__device__ __forceinline__ uint32_t sobol_fold(uint32_t r, const uint32_t *w) {
+#pragma unroll
+    for (int c = 0; c + 1 < NIB; c += 2) r = xor3(r, w[c], w[c + 1]);
+    if (NIB & 1) r ^= w[NIB - 1];
+    return r;
+}
+#define MTSG_NIB_SEQ(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12)
+static_assert(MTSG_NIBBLES == 13, "MTSG_NIB_SEQ lists the nibbles of the widest index");
+// one dimension's bits ^ r, from its LDS table
+template <int NIB>
+__device__ __forceinline__ uint32_t sobol_bits_lds(lds_u32 *tab, uint64_t index, uint32_t r) {
+    uint32_t w[NIB];
+#define MTSG_NIB(c) if constexpr (c < NIB) w[c < NIB ? c : 0] = sobol_row<c>(tab, index)[c * 16];
+    MTSG_NIB_SEQ(MTSG_NIB)
+#undef MTSG_NIB
+    return sobol_fold<NIB>(r, w);
+}
+// two successive dimensions of one index, both in LDS: their tables are NIB * 16
+// words apart, so the row addresses are formed once and (NIB = 8: 128 words,
+// within ds_read2_b32's second offset) each nibble's two words are one read
+template <int NIB>
+__device__ __forceinline__ void sobol_bits2_lds(lds_u32 *tab, uint64_t index, uint32_t r, uint32_t &b0, uint32_t &b1) {
+    uint32_t w0[NIB], w1[NIB];
+#define MTSG_NIB(c)                                              \
+    if constexpr (c < NIB) {                                     \
+        lds_u32 *p = sobol_row<c>(tab, index);                   \
+        w0[c < NIB ? c : 0] = p[c * 16];                         \
+        w1[c < NIB ? c : 0] = p[c * 16 + NIB * 16];              \
     }
-    const uint32_t result = C.scramble ^ bits;
+    MTSG_NIB_SEQ(MTSG_NIB)
+#undef MTSG_NIB
+    b0 = sobol_fold<NIB>(r, w0);
+    b1 = sobol_fold<NIB>(r, w1);
+}
+#undef MTSG_NIB_SEQ
+
+__device__ __forceinline__ float sobol_finish(uint32_t result) {
     float v = (float)result * (1.0f / 4294967296.0f);
     return smin(v, D_ONE_MINUS_EPS);
+}
+
+__device__ __forceinline__ float sobol_sample(const SobolCtx &C, uint64_t index, uint32_t dim) {
+    if (C.indep) return indep_float(index, dim);
+    uint32_t result;
+    if (dim < C.lds_dims) {
+        lds_u32 *t = C.lds + dim * C.nibbles * 16;
+        if (C.tight)
+            result = (C.nibbles == 8) ? sobol_bits_lds<8>(t, index, C.scramble)
+                                      : sobol_bits_lds<MTSG_NIBBLES>(t, index, C.scramble);
+        else
+            result = C.scramble ^ ((C.nibbles == 8) ? sobol_bits<8>(t, index) : sobol_bits<MTSG_NIBBLES>(t, index));
+    } else {
+        glb_u32 *t = C.glob + (size_t)dim * MTSG_NIBBLES * 16;
+        result = C.scramble ^ ((C.nibbles == 8) ? sobol_bits<8>(t, index) : sobol_bits<MTSG_NIBBLES>(t, index));
+    }
+    return sobol_finish(result);
+}
+
+// dimensions dim and dim + 1 of one index (next2d).  Both in the LDS tables: one
+// set of nibble offsets for the two (sobol_bits2_lds); any other case -- a pair
+// that straddles lds_dims, global tables, the independent sampler -- is two
+// sobol_sample draws.  The same words XORed in another order: the same bits.
+__device__ __forceinline__ void sobol_sample2(const SobolCtx &C, uint64_t index, uint32_t dim, float &u, float &v) {
+    if (C.tight && !C.indep && dim + 1 < C.lds_dims) {
+        lds_u32 *t = C.lds + dim * C.nibbles * 16;
+        uint32_t b0, b1;
+        if (C.nibbles == 8) sobol_bits2_lds<8>(t, index, C.scramble, b0, b1);
+        else sobol_bits2_lds<MTSG_NIBBLES>(t, index, C.scramble, b0, b1);
+        u = sobol_finish(b0);
+        v = sobol_finish(b1);
+        return;
+    }
+    u = sobol_sample(C, index, dim);
+    v = sobol_sample(C, index, dim + 1);
 }
 
 // sobol::look_up restated as the GF(2) solve it encodes (host precomputes inv/ycol)
@@ -555,10 +641,19 @@ __device__ __forceinline__ void scan_pair_k(cst_tri *tris, uint32_t n, uint32_t 
     }
 }
 
+// rS, rC: the rays' reciprocal directions as ray_interval's clip formed them.  A ray
+// that is on passed the clip's three axes, so each r_k with d_k != 0 is RN(1 / d_k), and
+// `fast` admits only such axes; a ray that is off (no ray, an early exit of the clip, an
+// empty interval) may carry anything there: its interval rejects every finite or
+// infinite quotient and its barycentric test a NaN one.
+// (-DMTSG_CLIP_RCP=0: scan_pair divides again, for A/B builds)
+#ifndef MTSG_CLIP_RCP
+#define MTSG_CLIP_RCP 1
+#endif
 template <bool STATS>
-__device__ __forceinline__ void scan_pair(const MtsgLaunch &L, f3 o, f3 ds, f3 dc, float minS, float maxS, float minC,
-                                          float maxC, bool &occ, bool &found, uint32_t &bestPrim, float &bu,
-                                          float &bv, float &bt, unsigned long long &tests) {
+__device__ __forceinline__ void scan_pair(const MtsgLaunch &L, f3 o, f3 ds, f3 dc, f3 rS, f3 rC, float minS, float maxS,
+                                          float minC, float maxC, bool &occ, bool &found, uint32_t &bestPrim,
+                                          float &bu, float &bv, float &bt, unsigned long long &tests) {
     cst_tri *tris = (cst_tri *)L.scan_tris;
     occ = false;
     found = false;
@@ -576,12 +671,13 @@ __device__ __forceinline__ void scan_pair(const MtsgLaunch &L, f3 o, f3 ds, f3 d
         tris += ng;                                                                                                \
         if (na) {                                                                                                  \
             const float s_k = K == 0 ? ds.x : K == 1 ? ds.y : ds.z, c_k = K == 0 ? dc.x : K == 1 ? dc.y : dc.z;    \
+            const float yS = MTSG_CLIP_RCP ? (K == 0 ? rS.x : K == 1 ? rS.y : rS.z) : 1.0f / s_k;                  \
+            const float yC = MTSG_CLIP_RCP ? (K == 0 ? rC.x : K == 1 ? rC.y : rC.z) : 1.0f / c_k;                  \
             const bool fast = (offS || (minS >= 0x1p-30f && fabsf(s_k) >= 0x1p-60f)) &&                            \
                               (offC || (minC >= 0x1p-30f && fabsf(c_k) >= 0x1p-60f));                              \
             if (__all(fast))                                                                                       \
                 scan_pair_k<K, true, true, STATS>(tris, na, L.scan_n[2 * K + 1] >> 16, o, ds, dc, minS, maxS,      \
-                                                  minC, occ, found, bestPrim, bu, bv, bt, tests, 1.0f / s_k,       \
-                                                  1.0f / c_k);                                                     \
+                                                  minC, occ, found, bestPrim, bu, bv, bt, tests, yS, yC);          \
             else                                                                                                   \
                 scan_pair_k<K, true, false, STATS>(tris, na, 0, o, ds, dc, minS, maxS, minC, occ, found,           \
                                                    bestPrim, bu, bv, bt, tests);                                   \
@@ -592,9 +688,12 @@ __device__ __forceinline__ void scan_pair(const MtsgLaunch &L, f3 o, f3 ds, f3 d
 #undef MTSG_SCAN_GROUP
 }
 
-// AABB::rayIntersect (core/aabb.h:308-338) against the scene bounds
-__device__ __forceinline__ bool aabb_clip(const MtsgDeviceScene &S, f3 o, f3 d, float &nearT, float &farT) {
+// AABB::rayIntersect (core/aabb.h:308-338) against the scene bounds.  dRcp: the
+// reciprocals 1 / d_i it formed (0 for an axis it did not reach or with d_i = 0);
+// after `true` every axis with d_i != 0 has its own
+__device__ __forceinline__ bool aabb_clip(const MtsgDeviceScene &S, f3 o, f3 d, float &nearT, float &farT, f3 &dRcp) {
     nearT = -INFINITY; farT = INFINITY;
+    dRcp = mk(0, 0, 0);
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const float origin = comp(o, i), di = comp(d, i);
@@ -603,6 +702,7 @@ __device__ __forceinline__ bool aabb_clip(const MtsgDeviceScene &S, f3 o, f3 d, 
             if (origin < minVal || origin > maxVal) return false;
         } else {
             const float rcp = (float)1 / di;                 // ray.dRcp (ray.h:86-93)
+            if (i == 0) dRcp.x = rcp; else if (i == 1) dRcp.y = rcp; else dRcp.z = rcp;
             float t1 = (minVal - origin) * rcp;
             float t2 = (maxVal - origin) * rcp;
             if (t1 > t2) { float t = t1; t1 = t2; t2 = t; }
@@ -767,9 +867,10 @@ __device__ bool kd_traverse(const uint2 *__restrict__ nodes, const uint32_t *__r
 
 // ShapeKDTree::rayIntersect (skdtree.cpp:112-142 closest, :207-226 shadow):
 // scene-AABB clip + adaptive ray epsilon -> [mint, maxt] for the traversal
+// (dRcp: aabb_clip's reciprocals, which scan_pair divides by)
 __device__ __forceinline__ bool ray_interval(const MtsgDeviceScene &S, f3 o, f3 d, float rmint, float rmaxt,
-                                             bool shadow, float &mint, float &maxt) {
-    if (!aabb_clip(S, o, d, mint, maxt)) return false;
+                                             bool shadow, float &mint, float &maxt, f3 &dRcp) {
+    if (!aabb_clip(S, o, d, mint, maxt, dRcp)) return false;
     float rayMinT = rmint;
     if (rayMinT == D_EPSILON) {
         if (shadow) rayMinT *= smax(smax(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
@@ -778,6 +879,11 @@ __device__ __forceinline__ bool ray_interval(const MtsgDeviceScene &S, f3 o, f3 
     if (rayMinT > mint) mint = rayMinT;
     if (rmaxt < maxt) maxt = rmaxt;
     return maxt > mint;
+}
+__device__ __forceinline__ bool ray_interval(const MtsgDeviceScene &S, f3 o, f3 d, float rmint, float rmaxt,
+                                             bool shadow, float &mint, float &maxt) {
+    f3 dRcp;
+    return ray_interval(S, o, d, rmint, rmaxt, shadow, mint, maxt, dRcp);
 }
 
 // computeShadingFrame (util.cpp:603-608); t = cross(n, s) is ShFrame::t()
@@ -1045,12 +1151,13 @@ __device__ __forceinline__ void next2d(const SobolCtx &C, float resolution, Samp
     if (s.dim + 1 >= 5 && s.dim < 5) s.dim = 5;   // skip the (empty) array dimensions [5,5)
     if (s.dim + 1 >= MTSG_SOBOL_DIMS && !C.indep) { s.err = true; u = v = 0.0f; return; }
     if (!C.indep && s.dim == 0 && s.sobolIndex != (uint64_t)s.sampleIndex) {
-        u = sobol_sample(C, s.sobolIndex, s.dim++) * resolution - (float)px;
-        v = sobol_sample(C, s.sobolIndex, s.dim++) * resolution - (float)py;
+        sobol_sample2(C, s.sobolIndex, s.dim, u, v);
+        u = u * resolution - (float)px;
+        v = v * resolution - (float)py;
     } else {
-        u = sobol_sample(C, s.sobolIndex, s.dim++);
-        v = sobol_sample(C, s.sobolIndex, s.dim++);
+        sobol_sample2(C, s.sobolIndex, s.dim, u, v);
     }
+    s.dim += 2;
 }
 
 __device__ __forceinline__ f3 xf_point(const float *m, f3 p) {         // transform.h:108-125
@@ -1251,6 +1358,11 @@ __device__ __forceinline__ LdsView<SCENE_LDS> lds_view(const MtsgLaunch &L, uint
     v.SC.scramble = L.scramble;
     v.SC.indep = L.sampler != MTSG_SAMPLER_SOBOL;
     v.SC.replay = L.replay != 0;
+#ifndef MTSG_NO_SOBOL_PAIRS   // (A/B builds: the draws as they were)
+    v.SC.tight = SCENE_LDS;
+#else
+    v.SC.tight = false;
+#endif
     v.SC.sfmt = L.sfmt;
     v.stackBase = base2 + sceneWords;
     return v;

@@ -58,7 +58,7 @@ __device__ __forceinline__ f3 field_albedo(const MtsgDeviceScene &S, GBsdf &top,
 template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLaunch L, MtsgFieldArgs FA) {
     constexpr bool ANA = (FEAT & MTSG_FEAT_ANA) != 0;
-    extern __shared__ uint32_t lds[];
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
     lds_u32 *ycolTab = V.ycolTab;

@@ -203,7 +203,7 @@ template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLaunch L) {
     constexpr bool ENV = (FEAT & MTSG_FEAT_ENV) != 0, EXT = (FEAT & MTSG_FEAT_EXT) != 0,
                    ANA = (FEAT & MTSG_FEAT_ANA) != 0;
-    extern __shared__ uint32_t lds[];
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     // LDS as path_kernel: [Sobol nibble tables][look_up tables][scene (small scenes)][stacks]
     const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
@@ -375,7 +375,7 @@ template <bool ANY, int WAVES, bool ANA>
 __global__ __launch_bounds__(BLOCK, WAVES) void trace_kernel(MtsgDeviceScene S, const float4 *__restrict__ rays,
                                                               uint32_t n, float4 *__restrict__ out,
                                                               uint32_t stackDepth) {
-    extern __shared__ uint32_t lds[];
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     lds_stk_n *stkN = (lds_stk_n *)lds + threadIdx.x;
     lds_stk_d *stkD = (lds_stk_d *)(lds + stackDepth * BLOCK) + threadIdx.x;
     unsigned long long cn = 0, ct = 0;

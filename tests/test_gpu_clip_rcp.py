@@ -1,0 +1,99 @@
+"""One reciprocal per ray and axis (dpath.h aabb_clip -> scan_pair): the scene-bounds clip
+hands its three 1 / d to the tiny-scene scan, which divides by them in its axis-aligned
+groups instead of forming them again.  Scan scenes (<= 64 triangles) in which the clip's
+paths differ between the lanes of one wave:
+
+* a camera outside the box with a wide field of view: many primary rays miss the scene
+  bounds (the clip's early exits), their neighbours do not;
+* a camera along +z at sample 0 with scramble 0: the Sobol point is 0, the sample sits on
+  the pixel corner, and the centre column's and row's directions have a component that is
+  exactly zero (the clip's d == 0 branch; such a wave takes the scan's slow aligned pass);
+* a light panel tilted 2.5e-18 out of the plane x = 0 above the wall that lies in that
+  plane: shadow rays from the wall have 0 < |d.x| < 2^-60, a reciprocal near 1e19 and the
+  slow aligned pass, next to lanes that shade the other surfaces.  (The panel is bright
+  enough that the two cosines of ~1e-18 leave a normal float, so emitter sampling always
+  picks it.)
+
+Every render is compared bit for bit with the oracle (per-sample records, film, counters)
+and with the same render under MTSGPU_NO_SCAN_PAIRS=1."""
+import numpy as np
+import pytest
+
+from mitsuba_amd import scenes
+from mitsuba_amd.integrator import scan_host
+from mitsuba_amd.scene import Emitter, Mesh
+
+pytestmark = pytest.mark.gpu
+
+COUNTERS = ('samples', 'rays', 'shadow_rays', 'path_length_sum')
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _wide_fov():
+    sc, it = scenes.build('C1', width=48, height=32, spp=4, rfilter='box')
+    sc.sensor.fov = 120.0
+    return sc, it
+
+
+def _axis_camera():
+    sc, it = scenes.build('C1', width=32, height=32, spp=1, rfilter='box')
+    assert it.scramble == 0
+    d = np.asarray(sc.sensor.toWorld, np.float32)[:3, 2]
+    assert d.tolist() == [0.0, 0.0, 1.0]   # the camera looks along +z
+    return sc, it
+
+
+def _grazing_light():
+    sc, it = scenes.build('C1', width=32, height=32, spp=4, rfilter='box')
+    green = sc.meshes[3]
+    assert (np.asarray(green.positions)[:, 0] == 0).all()   # the wall in the plane x = 0
+    # facing +x, its far vertex 1e-18 out of the wall's plane; bright enough that the two
+    # cosines of ~1e-18 and ~1e-19 leave a normal float
+    panel = np.array([[0.0, 5.6, 1.0], [0.0, 5.6, 4.0], [1e-18, 6.0, 2.5]], np.float32)
+    sc.emitters = list(sc.emitters) + [Emitter('area', radiance=(1e20, 1e20, 1e20))]
+    sc.meshes = list(sc.meshes) + [Mesh(panel, np.array([[0, 1, 2]], np.uint32), bsdf=-1, emitter=1, faceNormals=True)]
+    return sc, it
+
+
+SCENES = {'wide_fov': _wide_fov, 'axis_camera': _axis_camera, 'grazing_light': _grazing_light}
+
+
+def _render_both(ctx, sc, it, monkeypatch, instr):
+    out = []
+    for off in (False, True):
+        if off:
+            monkeypatch.setenv('MTSGPU_NO_SCAN_PAIRS', '1')
+        else:
+            monkeypatch.delenv('MTSGPU_NO_SCAN_PAIRS', raising=False)
+        ctx.upload(sc)
+        out.append(ctx.render(it, samples=instr) + (ctx.kernel_variant(),))
+    monkeypatch.delenv('MTSGPU_NO_SCAN_PAIRS', raising=False)
+    return out
+
+
+@pytest.mark.parametrize('instr', [True, False], ids=['instr', 'plain'])
+@pytest.mark.parametrize('name', sorted(SCENES))
+def test_clip_reciprocals_reach_the_scan_bitexact(gpu_ctx, oracle, monkeypatch, name, instr):
+    sc, it = SCENES[name]()
+    assert sc.num_triangles <= 64
+    n = scan_host(sc)[1]
+    assert sum(n[1::2]) > 0   # axis-aligned groups: where the scan divides by the clip's reciprocals
+    (film_p, smp_p, st_p, v_p), (film_s, smp_s, st_s, v_s) = _render_both(gpu_ctx, sc, it, monkeypatch, instr)
+    assert v_p['scene_lds'] and v_p['instr'] == instr and v_p == v_s
+    film_o, smp_o, st_o = oracle.render(sc, it, samples=True, libm_mode=0)
+    if instr:
+        for smp in (smp_p, smp_s):
+            same = np.all(_bits(smp) == _bits(smp_o), axis=1)
+            bad = np.nonzero(~same)[0]
+            assert same.all(), (bad.size, same.size, bad[:3], smp[bad[:2]], smp_o[bad[:2]])
+    assert np.array_equal(_bits(film_p), _bits(film_o)), np.argwhere(_bits(film_p) != _bits(film_o))[:4]
+    assert np.array_equal(_bits(film_p), _bits(film_s))
+    for k in COUNTERS:
+        assert st_p[k] == st_s[k] == st_o[k], k
+    if name == 'wide_fov':
+        assert st_p['rays'] < 2 * st_p['samples']        # most primary rays leave without a bounce
+    if name == 'grazing_light':
+        assert st_p['shadow_rays'] > st_p['samples']
