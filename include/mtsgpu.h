@@ -569,7 +569,9 @@ int mtsgpu_debug_libm(mtsgpu_ctx *ctx, int fn, const float *a, const float *b, f
    path lengths, node visits, TriAccel tests, dimension errors, hits, 8: the
    launches the render's sample count was split into -- the chunks of the
    per-sample record budget, written by the host, 1 when all samples fit --, NEE
-   samples, Sobol HBM words, diagnostic section cycles 11-14), and in 15 the
+   samples, Sobol HBM words, in 11 the production passes of the tiny-scene
+   megakernel's start queue (0: the launch did not take the queue), or in
+   diagnostic builds section cycles 11-14), and in 15 the
    kernel that ran: the megakernel's feature set (MTSG_FEAT_* bits of
    csrc/layout.h, BSDF-set bits included) | waves/SIMD << 8 | scene in LDS << 12,
    1 << 16 for the wavefront engine, or 1 << 17 | scene in LDS << 12 after a

@@ -3,10 +3,16 @@
 // SamplingIntegrator::renderBlock, src/librender/integrator.cpp:140-188),
 // instantiated per scene feature set in path_f.hip:
 //
-//  * lane g of the persistent grid takes sample runs g, g + lanes, g + 2 lanes, ...
-//    (static striding: no queue, no tail of long per-pixel tasks), a run being
+//  * lane g of the persistent grid owns sample runs g, g + lanes, g + 2 lanes, ...
+//    (static striding: no global queue, no tail of long per-pixel tasks), a run being
 //    2^round_shift consecutive samples of one pixel, one after the other;
 //  * a lane whose path ends starts its next item immediately (regeneration);
+//  * tiny scenes that are scanned (SCENE_LDS kernels, L.scan, not the SFMT replay)
+//    start paths a wave at a time instead: the wave's 64 lanes run one step of their
+//    item streams together, the real samples' start records go to a per-wave batch in
+//    LDS, and a lane whose path ends pops the next record, whichever lane produced it
+//    (mtsg_start_queue, DESIGN.md 4 "Start queue"); these kernels store every splat
+//    record as it is formed (no held pair);
 //  * each loop iteration traces the lane's pending shadow ray and its
 //    closest-hit ray, then shades (PathShader, dpath.h);
 //  * LDS holds the Sobol and look_up tables and the lane-strided traversal stacks
@@ -16,7 +22,8 @@
 
 size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // path_kernel.hip
 
-// tiny-scene kernels keep a pair's first splat record in registers (PathShader::finish)
+// tiny-scene kernels built without the start queue (-DMTSG_START_QUEUE=0) keep a pair's
+// first splat record in registers (PathShader::finish)
 #ifndef MTSG_HOLD_PAIR
 #define MTSG_HOLD_PAIR 1
 #endif
@@ -41,6 +48,11 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // path_kernel.hip
 #endif
 
 
+// a lane's rank among the lanes of `mask` below it
+__device__ __forceinline__ uint32_t wave_rank(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 // The persistent megakernel: grid = CUs x resident blocks; every lane runs
 // PathShader steps with both traversals inline
 template <bool INSTR, bool SCENE_LDS, int FEAT, int WAVES>
@@ -56,6 +68,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     // static striding: lane g takes sample runs g + k * lanes, k = 0, 1, ... (`round` is
     // the carried run state of layout.h mtsg_run_step, or the SFMT replay's position in
     // its unit: 32 bits, not a 64-bit item index, live across the bounce loop)
+    // Kernels with the start queue: `round` and prodPix are the lane's PRODUCER state (its
+    // item stream, unchanged); st.pix belongs to whatever path the lane renders
+    constexpr bool QUEUE = SCENE_LDS && MTSG_START_QUEUE;
     const uint32_t g = xcd_block(L.xcds) * BLOCK + threadIdx.x;
     uint32_t round = 0;
     bool done = false;
@@ -64,6 +79,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     st.active = false;
     st.pix = 0;
     if (!L.replay) mtsg_run_init(L, g, round, st.pix);   // the lane's one division
+    uint32_t prodPix = st.pix;
+    uint32_t qHead = 0, qCount = 0, qPasses = 0;   // wave-uniform: the batch's unread entries, production passes
     st.smp.sobolIndex = 0; st.smp.sampleIndex = 0; st.smp.dim = 0; st.smp.err = false;
     st.sx = st.sy = 0;
     st.haveRay = st.primary = st.haveShadow = false;
@@ -87,6 +104,84 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
         lds_stk_d *stkD = (lds_stk_d *)(lds + V.stackBase + L.stack_depth * BLOCK) + threadIdx.x;
         const PathShader<INSTR, SCENE_LDS, FEAT> sh{L, V.hs, V.SC, V.ycolTab, c};
         // ---- A: start the next sample
+        if (QUEUE && mtsg_start_queue(L)) {
+            // From the wave's start queue.  The wave's items are those its 64 lanes own
+            // (lane i's k-th mtsg_run_step is item (i, k)); a sample's result depends on
+            // (pixel, sample) alone and goes to that sample's own record slots, so which
+            // lane renders which item changes nothing.  A production pass runs step k of
+            // every lane that has items left, all lanes at once, and compacts the real
+            // samples' start records (no padding pixel, no missing sample of an odd run)
+            // into the batch; the lanes whose path has ended pop the next entries, by their
+            // rank among themselves.  An empty batch is refilled while lanes still need an
+            // entry and a lane still has items.
+            lds_w32 *q = (lds_w32 *)(lds + V.stackBase) + (threadIdx.x >> 6) * (MTSG_QUEUE_REC_WORDS * 64);
+            bool want = !st.active;
+            while (true) {
+                const uint64_t need = __ballot(want);
+                if (need == 0) break;
+                if (qCount == 0) {
+                    if (__all(done)) break;
+                    uint32_t jj = 0;
+                    int px = 0, py = 0;
+                    bool real = false;
+                    if (!done) {
+                        if (!mtsg_run_step(L, round, prodPix, jj)) done = true;
+                        else real = jj < L.chunk_spp && pixel_of(L, prodPix, px, py);
+                    }
+                    const uint64_t made = __ballot(real);
+                    if (real) {
+                        StartRec r;
+                        // A pass runs beside every lane's live path state.  Indices beyond 32
+                        // bits draw the film position one dimension at a time (the same words
+                        // XORed, the same bits): the paired draw's 26 words in flight made the
+                        // bench kernel spill (4 VGPRs; 124 and none with this)
+                        SobolCtx SCq = V.SC;
+                        SCq.tight = V.SC.nibbles == 8;
+                        const PathShader<INSTR, SCENE_LDS, FEAT> shq{L, V.hs, SCq, V.ycolTab, c};
+                        shq.produce(r, jj, prodPix, px, py);
+                        lds_w32 *w = q + wave_rank(made);   // slot < 64, words 0..9: within MTSG_QUEUE_WORDS
+                        w[0 * 64] = (uint32_t)r.sobolIndex;
+                        w[1 * 64] = (uint32_t)(r.sobolIndex >> 32);
+                        w[2 * 64] = __float_as_uint(r.sx);
+                        w[3 * 64] = __float_as_uint(r.sy);
+                        w[4 * 64] = __float_as_uint(r.rd.x);
+                        w[5 * 64] = __float_as_uint(r.rd.y);
+                        w[6 * 64] = __float_as_uint(r.rd.z);
+                        w[7 * 64] = __float_as_uint(r.invZ);
+                        w[8 * 64] = r.pix;
+                        w[9 * 64] = r.jj;
+                    }
+                    // the batch is written before any lane of the wave pops it
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    qHead = 0;
+                    qCount = (uint32_t)__popcll(made);
+                    ++qPasses;
+                    if (qCount == 0) continue;   // every item of the pass was padding
+                }
+                const uint32_t rank = wave_rank(need);
+                if (want && rank < qCount) {   // entry qHead + rank < qHead + qCount <= 64
+                    lds_w32 *e = q + qHead + rank;
+                    StartRec r;
+                    r.sobolIndex = (uint64_t)e[0 * 64] | ((uint64_t)e[1 * 64] << 32);
+                    r.sx = __uint_as_float(e[2 * 64]);
+                    r.sy = __uint_as_float(e[3 * 64]);
+                    r.rd = mk(__uint_as_float(e[4 * 64]), __uint_as_float(e[5 * 64]), __uint_as_float(e[6 * 64]));
+                    r.invZ = __uint_as_float(e[7 * 64]);
+                    r.pix = e[8 * 64];
+                    r.jj = e[9 * 64];
+                    r.dim = 2;   // produce() drew the film position (not the replay: dimensions 0, 1)
+                    sh.load(st, r);
+                    want = false;
+                }
+                const uint32_t n = min((uint32_t)__popcll(need), qCount);
+                qHead += n;
+                qCount -= n;
+            }
+            // no lane got a path: the items are exhausted and the batch is empty
+            if (!__any(st.active)) break;
+        } else {
         while (!st.active && !done) {
             if (L.replay) {   // SFMT replay: this lane's unit, pixel after pixel, in order
                 const uint32_t unit = blockIdx.x * BLOCK + threadIdx.x;
@@ -110,6 +205,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
             if (jj < L.chunk_spp) sh.start_jp(st, jj, st.pix);
         }
         if (__all(done)) break;
+        }
         MK_STAMP(mkT[0], mkT0);
 
         // ---- B: trace the shadow ray, then the closest-hit ray ---------------
@@ -201,7 +297,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
         bool ended = false;
         if (st.active && sh.shade(st, occluded, hit, slot, prim, hu, hv, ht)) {
             ended = true;
-            sh.template finish<false>(st, MTSG_HOLD_PAIR && SCENE_LDS ? &held : nullptr);
+            // (the held pair needs one lane to render a run's two samples back to back: not
+            // with the start queue, whose kernels store every record as it is formed)
+            sh.template finish<false>(st, MTSG_HOLD_PAIR && SCENE_LDS && !QUEUE ? &held : nullptr);
         }
         wc.len += wave_count(was && st.P.depth != d0);
         wc.samples += wave_count(ended);
@@ -216,6 +314,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     wc.len += wc.samples;
     wave_counters_flush(L, wc);
     path_counters_flush<STATS>(L, c);
+#ifndef MTSG_MK_STAMPS
+    // debug counter 11: the start queue's production passes (tests: a render took the queue)
+    if (QUEUE && qPasses && lane_id() == 0) atomicAdd(L.counters + 11, (unsigned long long)qPasses);
+#endif
 #ifdef MTSG_MK_STAMPS
     if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0)
         for (int k = 0; k < 4; ++k) atomicAdd(L.counters + 11 + k, mkT[k]);

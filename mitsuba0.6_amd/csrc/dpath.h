@@ -1252,6 +1252,35 @@ struct PathState {
     float rmint, rmaxt, smaxt;
 };
 
+// What a path needs to begin (PathShader::produce -> load): the sample's sequence
+// index (or stream key), film position, camera ray direction and 1 / dl.z (the ray's
+// interval is near_clip * invZ .. far_clip * invZ, re-formed by load), its compact
+// pixel and its sample of the chunk; dim: the sampler dimensions produce() consumed
+struct StartRec {
+    uint64_t sobolIndex;
+    float sx, sy;
+    f3 rd;
+    float invZ;
+    uint32_t pix, jj, dim;
+};
+
+// The tiny-scene megakernel's start queue (dmega.h): per wave one batch of up to 64
+// start records in LDS, structure-of-arrays (word w of slot s at [w * 64 + s]: a wave's
+// writes and pops touch 64 consecutive words, no bank conflict).  It lies where the
+// traversal stacks would (LdsView::stackBase), which a scanning launch never touches.
+// -DMTSG_START_QUEUE=0 (A/B builds): the loop without it
+#ifndef MTSG_START_QUEUE
+#define MTSG_START_QUEUE 1
+#endif
+#define MTSG_QUEUE_REC_WORDS 10   // sobolIndex (2), sx, sy, rd (3), invZ, pix, jj
+#define MTSG_QUEUE_WORDS ((BLOCK / 64) * MTSG_QUEUE_REC_WORDS * 64)   // per block
+// whether a launch of a SCENE_LDS megakernel starts its paths from the queue: scanning
+// launches only (the others need the stacks' LDS), and not the SFMT replay (a lane's
+// draws follow the order of its own unit)
+__host__ __device__ __forceinline__ bool mtsg_start_queue(const MtsgLaunch &L) {
+    return MTSG_START_QUEUE && L.scene_lds && L.scan && !L.replay && L.integrator != MTSG_INTEGRATOR_DIRECT;
+}
+
 // per-lane counts: 32-bit for the always-on ones (fewer live VGPRs in the
 // persistent loop; finish() flushes them long before they could wrap),
 // 64-bit for the INSTR-only traversal statistics
@@ -1418,13 +1447,19 @@ struct PathShader {
     }
 
     __device__ __forceinline__ void begin(PathState &st, uint32_t jj, const int px, const int py) const {
+        StartRec r;
+        produce(r, jj, st.pix, px, py);
+        load(st, r);
+    }
+
+    // begin()'s producing half: the sample's sequence index, its film position and its
+    // camera ray, which depend on (pixel, sample) alone -- any lane may form them (the
+    // tiny-scene megakernel: all 64 lanes of a wave at once, dmega.h).  Not for the SFMT
+    // replay, whose draws belong to the rendering lane's stream
+    __device__ __forceinline__ void produce(StartRec &r, uint32_t jj, uint32_t pix, const int px, const int py) const {
         const MtsgDeviceScene &S = L.scene;
-        SamplerState &smp = st.smp;
-        PathVars &P = st.P;
+        SamplerState smp;
         const uint32_t j = L.j0 + jj;
-        float &sx = st.sx, &sy = st.sy;
-        f3 &rd = st.rd;
-        float &rmint = st.rmint, &rmaxt = st.rmaxt;
         smp.dim = 0;
         smp.sampleIndex = j;
         smp.err = false;
@@ -1436,20 +1471,41 @@ struct PathShader {
             smp.sobolIndex = j;
         float u, v;
         next2d(SC, L.resolution, smp, px, py, u, v);
-        sx = (float)px + u;
-        sy = (float)py + v;
+        r.sobolIndex = smp.sobolIndex;
+        r.dim = smp.dim;
+        r.jj = jj;
+        r.pix = pix;
+        r.sx = (float)px + u;
+        r.sy = (float)py + v;
         // PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298)
         const MtsgCamera &cam = S.cam;
-        const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
+        const f3 nearP = xf_point(cam.sample_to_camera, mk(r.sx * cam.inv_res_x, r.sy * cam.inv_res_y, 0.0f));
         const f3 dl = normalize(nearP);
-        const float invZ = 1.0f / dl.z;
-        rmint = cam.near_clip * invZ;
-        rmaxt = cam.far_clip * invZ;
+        r.invZ = 1.0f / dl.z;
+        const float *W = cam.to_world;
+        r.rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
+                  W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
+    }
+
+    // begin()'s other half: a start record into the path state, the camera origin and
+    // Li()'s prologue
+    __device__ __forceinline__ void load(PathState &st, const StartRec &r) const {
+        const MtsgCamera &cam = L.scene.cam;
+        SamplerState &smp = st.smp;
+        PathVars &P = st.P;
+        st.pix = r.pix;
+        smp.sobolIndex = r.sobolIndex;
+        smp.sampleIndex = L.j0 + r.jj;
+        smp.dim = r.dim;
+        smp.err = false;   // (the first next2d cannot run out of dimensions)
+        st.sx = r.sx;
+        st.sy = r.sy;
+        st.rd = r.rd;
+        st.rmint = cam.near_clip * r.invZ;
+        st.rmaxt = cam.far_clip * r.invZ;
         const float *W = cam.to_world;
         P.its.p = mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
                      W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);   // the ray's origin
-        rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
-                W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
         // Li() prologue (path.cpp:119-133)
         P.L = mk(0, 0, 0);
         P.thr = mk(1.0f, 1.0f, 1.0f);

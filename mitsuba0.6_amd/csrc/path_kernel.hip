@@ -686,7 +686,10 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
     const size_t scene = L.scene_lds ? ((size_t)L.num_nodes * 16 + (size_t)L.scene.num_prims * (12 + 10) +
                                         (size_t)L.num_verts * 6 + (size_t)L.num_shapes * (sizeof(MtsgShape) / 4))
                                      : 0;
-    return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS + scene + ((size_t)L.stack_depth * 3 * BLOCK + 1) / 2) * 4;
+    // the traversal stacks, or in their place the megakernel's start queue (dpath.h mtsg_start_queue)
+    size_t tail = ((size_t)L.stack_depth * 3 * BLOCK + 1) / 2;
+    if (mtsg_start_queue(L)) tail = std::max<size_t>(tail, MTSG_QUEUE_WORDS);
+    return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS + scene + tail) * 4;
 }
 
 // the megakernel variants, one object per scene feature set (path_f.hip)
