@@ -570,8 +570,10 @@ int mtsgpu_debug_libm(mtsgpu_ctx *ctx, int fn, const float *a, const float *b, f
    launches the render's sample count was split into -- the chunks of the
    per-sample record budget, written by the host, 1 when all samples fit --, NEE
    samples, Sobol HBM words, in 11 the production passes of the tiny-scene
-   megakernel's start queue (0: the launch did not take the queue), or in
-   diagnostic builds section cycles 11-14), and in 15 the
+   megakernel's start queue (0: the launch did not take the queue) and in 12 the
+   samples those passes finished themselves because their camera ray misses the
+   scene (0 under an environment emitter) -- or in diagnostic builds section
+   cycles 11-14 --), and in 15 the
    kernel that ran: the megakernel's feature set (MTSG_FEAT_* bits of
    csrc/layout.h, BSDF-set bits included) | waves/SIMD << 8 | scene in LDS << 12,
    1 << 16 for the wavefront engine, or 1 << 17 | scene in LDS << 12 after a

@@ -13,6 +13,11 @@
 //    LDS, and a lane whose path ends pops the next record, whichever lane produced it
 //    (mtsg_start_queue, DESIGN.md 4 "Start queue"); these kernels store every splat
 //    record as it is formed (no held pair);
+//  * in kernels without an environment emitter a production pass retires the samples
+//    whose camera ray fails section B's own ray_interval test (the scene bounds and the
+//    clip planes): such a path is black at depth 1 with one ray, so the pass writes its
+//    records and counts it, and only the other samples enter the batch (MTSG_EARLY_MISS,
+//    DESIGN.md 4 "Early miss");
 //  * each loop iteration traces the lane's pending shadow ray and its
 //    closest-hit ray, then shades (PathShader, dpath.h);
 //  * LDS holds the Sobol and look_up tables and the lane-strided traversal stacks
@@ -53,6 +58,20 @@ __device__ __forceinline__ uint32_t wave_rank(uint64_t mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// a start record into its slot of the wave's batch (word w of slot s at [w * 64 + s])
+__device__ __forceinline__ void queue_store(lds_w32 *w, const StartRec &r) {
+    w[0 * 64] = (uint32_t)r.sobolIndex;
+    w[1 * 64] = (uint32_t)(r.sobolIndex >> 32);
+    w[2 * 64] = __float_as_uint(r.sx);
+    w[3 * 64] = __float_as_uint(r.sy);
+    w[4 * 64] = __float_as_uint(r.rd.x);
+    w[5 * 64] = __float_as_uint(r.rd.y);
+    w[6 * 64] = __float_as_uint(r.rd.z);
+    w[7 * 64] = __float_as_uint(r.invZ);
+    w[8 * 64] = r.pix;
+    w[9 * 64] = r.jj;
+}
+
 // The persistent megakernel: grid = CUs x resident blocks; every lane runs
 // PathShader steps with both traversals inline
 template <bool INSTR, bool SCENE_LDS, int FEAT, int WAVES>
@@ -71,6 +90,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     // Kernels with the start queue: `round` and prodPix are the lane's PRODUCER state (its
     // item stream, unchanged); st.pix belongs to whatever path the lane renders
     constexpr bool QUEUE = SCENE_LDS && MTSG_START_QUEUE;
+    // a production pass retires the samples whose camera ray misses the scene: without an
+    // environment emitter their record is known once the ray exists
+    constexpr bool EARLY = QUEUE && MTSG_EARLY_MISS && (FEAT & MTSG_FEAT_ENV) == 0;
     const uint32_t g = xcd_block(L.xcds) * BLOCK + threadIdx.x;
     uint32_t round = 0;
     bool done = false;
@@ -81,6 +103,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     if (!L.replay) mtsg_run_init(L, g, round, st.pix);   // the lane's one division
     uint32_t prodPix = st.pix;
     uint32_t qHead = 0, qCount = 0, qPasses = 0;   // wave-uniform: the batch's unread entries, production passes
+    uint32_t qRetired = 0;                         // wave-uniform: samples the passes finished themselves
     st.smp.sobolIndex = 0; st.smp.sampleIndex = 0; st.smp.dim = 0; st.smp.err = false;
     st.sx = st.sy = 0;
     st.haveRay = st.primary = st.haveShadow = false;
@@ -128,7 +151,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
                         if (!mtsg_run_step(L, round, prodPix, jj)) done = true;
                         else real = jj < L.chunk_spp && pixel_of(L, prodPix, px, py);
                     }
-                    const uint64_t made = __ballot(real);
+                    uint64_t made;   // the lanes whose sample enters the batch
+                    if constexpr (!EARLY) {
+                    made = __ballot(real);
                     if (real) {
                         StartRec r;
                         // A pass runs beside every lane's live path state.  Indices beyond 32
@@ -139,17 +164,39 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
                         SCq.tight = V.SC.nibbles == 8;
                         const PathShader<INSTR, SCENE_LDS, FEAT> shq{L, V.hs, SCq, V.ycolTab, c};
                         shq.produce(r, jj, prodPix, px, py);
-                        lds_w32 *w = q + wave_rank(made);   // slot < 64, words 0..9: within MTSG_QUEUE_WORDS
-                        w[0 * 64] = (uint32_t)r.sobolIndex;
-                        w[1 * 64] = (uint32_t)(r.sobolIndex >> 32);
-                        w[2 * 64] = __float_as_uint(r.sx);
-                        w[3 * 64] = __float_as_uint(r.sy);
-                        w[4 * 64] = __float_as_uint(r.rd.x);
-                        w[5 * 64] = __float_as_uint(r.rd.y);
-                        w[6 * 64] = __float_as_uint(r.rd.z);
-                        w[7 * 64] = __float_as_uint(r.invZ);
-                        w[8 * 64] = r.pix;
-                        w[9 * 64] = r.jj;
+                        queue_store(q + wave_rank(made), r);   // slot < 64, words 0..9: within MTSG_QUEUE_WORDS
+                    }
+                    } else {
+                    // The same pass, which also retires.  The record stays inside the branch
+                    // of the real lanes and its two ends are an if / else there (kept with r
+                    // live across the wave's ballot and the retirement after the stores, the
+                    // bench kernel spilled 9 VGPRs; 125 and none like this).  `keep` is false
+                    // in the lanes that skip the branch, so a ballot inside it and the one
+                    // after it see the same lanes.  A wave cannot retire 2^31 samples in one
+                    // launch (their records alone would be 32 GiB), so wc needs no flush here
+                    bool keep = real;
+                    if (real) {
+                        StartRec r;
+                        SobolCtx SCq = V.SC;
+                        SCq.tight = V.SC.nibbles == 8;
+                        const PathShader<INSTR, SCENE_LDS, FEAT> shq{L, V.hs, SCq, V.ycolTab, c};
+                        shq.produce(r, jj, prodPix, px, py);
+                        // section B's own test of this camera ray (the operands load() forms,
+                        // the same function): false here is okC false there, a path that
+                        // shade() ends black at depth 1 -- its records are written now and it
+                        // never takes a lane
+                        float mn, mx;
+                        keep = ray_interval(S, shq.cam_origin(), r.rd, S.cam.near_clip * r.invZ,
+                                            S.cam.far_clip * r.invZ, false, mn, mx);
+                        if (keep) queue_store(q + wave_rank(__ballot(keep)), r);
+                        else shq.retire(r, px, py);
+                    }
+                    // a retired sample: its one ray, no path length beyond its own 1
+                    const uint32_t nr = wave_count(real && !keep);
+                    wc.rays += nr;
+                    wc.samples += nr;
+                    qRetired += nr;
+                    made = __ballot(keep);
                     }
                     // the batch is written before any lane of the wave pops it
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -158,7 +205,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
                     qHead = 0;
                     qCount = (uint32_t)__popcll(made);
                     ++qPasses;
-                    if (qCount == 0) continue;   // every item of the pass was padding
+                    // every item of the pass was padding or retired: the next pass (a wave that
+                    // never queues a record leaves by __all(done) and the test after the loop)
+                    if (qCount == 0) continue;
                 }
                 const uint32_t rank = wave_rank(need);
                 if (want && rank < qCount) {   // entry qHead + rank < qHead + qCount <= 64
@@ -317,6 +366,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
 #ifndef MTSG_MK_STAMPS
     // debug counter 11: the start queue's production passes (tests: a render took the queue)
     if (QUEUE && qPasses && lane_id() == 0) atomicAdd(L.counters + 11, (unsigned long long)qPasses);
+    // debug counter 12: the samples retired in production passes
+    if (EARLY && qRetired && lane_id() == 0) atomicAdd(L.counters + 12, (unsigned long long)qRetired);
 #endif
 #ifdef MTSG_MK_STAMPS
     if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0)

@@ -1272,6 +1272,12 @@ struct StartRec {
 #ifndef MTSG_START_QUEUE
 #define MTSG_START_QUEUE 1
 #endif
+// A production pass finishes the samples whose camera ray misses the scene itself,
+// instead of queueing them (dmega.h; kernels without MTSG_FEAT_ENV).
+// -DMTSG_EARLY_MISS=0 (A/B builds): every real sample is queued
+#ifndef MTSG_EARLY_MISS
+#define MTSG_EARLY_MISS 1
+#endif
 #define MTSG_QUEUE_REC_WORDS 10   // sobolIndex (2), sx, sy, rd (3), invZ, pix, jj
 #define MTSG_QUEUE_WORDS ((BLOCK / 64) * MTSG_QUEUE_REC_WORDS * 64)   // per block
 // whether a launch of a SCENE_LDS megakernel starts its paths from the queue: scanning
@@ -1487,6 +1493,13 @@ struct PathShader {
                   W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
     }
 
+    // every camera ray's origin (wave-uniform)
+    __device__ __forceinline__ f3 cam_origin() const {
+        const float *W = L.scene.cam.to_world;
+        return mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
+                  W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);
+    }
+
     // begin()'s other half: a start record into the path state, the camera origin and
     // Li()'s prologue
     __device__ __forceinline__ void load(PathState &st, const StartRec &r) const {
@@ -1503,9 +1516,7 @@ struct PathShader {
         st.rd = r.rd;
         st.rmint = cam.near_clip * r.invZ;
         st.rmaxt = cam.far_clip * r.invZ;
-        const float *W = cam.to_world;
-        P.its.p = mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
-                     W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);   // the ray's origin
+        P.its.p = cam_origin();   // the ray's origin
         // Li() prologue (path.cpp:119-133)
         P.L = mk(0, 0, 0);
         P.thr = mk(1.0f, 1.0f, 1.0f);
@@ -1893,6 +1904,27 @@ struct PathShader {
         }
         st.active = false;
         st.haveRay = st.haveShadow = false;
+    }
+
+    // The whole path of a sample whose camera ray misses the scene (the start queue's
+    // production pass, dmega.h; kernels without ENV only): what load(), one shade() and
+    // finish<false>() leave for it -- Li = 0, alpha 0 (1 without has_alpha), depth 1, the
+    // two film dimensions drawn.  px, py: the sample's pixel (pixel_of(r.pix))
+    __device__ __forceinline__ void retire(const StartRec &r, const int px, const int py) const {
+        static_assert(!ENV, "a miss under an environment emitter is not black");
+        const bool a = !L.has_alpha;
+        const float alpha = a ? 1.0f : 0.0f;
+        const float val[5] = {0.0f, 0.0f, 0.0f, alpha, 1.0f};
+        // (the per-sample record first: stored after film_record, the instrumented 4-wave
+        // kernel spilled 9 VGPRs instead of 6)
+        if (INSTR && L.samples) {
+            const uint32_t pixIdx = (uint32_t)(py - (int)L.y0) * L.width + (uint32_t)(px - (int)L.x0);
+            float *rec = L.samples + ((size_t)pixIdx * L.spp + (L.j0 + r.jj)) * 8;
+            rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f; rec[3] = alpha;
+            rec[4] = r.sx; rec[5] = r.sy; rec[6] = 1.0f; rec[7] = 0.0f;
+        }
+        film_record(L, film_slot(L, r.jj, r.pix), px, py, r.sx, r.sy, val, a);
+        if (STATS) c.sobol += (unsigned long long)r.dim * (r.dim < L.lds_dims ? 0 : L.nibbles);
     }
 };
 
