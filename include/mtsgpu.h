@@ -552,6 +552,25 @@ int mtsgpu_index_host(const uint32_t geom[11], const uint32_t *lane_round, size_
  * through the tables the kernels stage: out[i] = the sequence index of sample j at pixel
  * (px, py), for the triples {px, py, j} of `px_py_j`. */
 int mtsgpu_lookup_host(uint32_t m, uint64_t scramble, const uint32_t *px_py_j, size_t n, uint64_t *out);
+/* Host-only (no device needed): what mtsgpu_render (num_fields = 0) or mtsgpu_render_fields
+ * (num_fields fields) would launch for `params` on `scene`, by the planning functions the
+ * renders run, under the MTSGPU_* environment of the call.  want_samples: per-sample records
+ * are asked for.  dev = {CUs of the device, resident blocks per CU of the persistent kernel
+ * (0: the plan's waves per SIMD), free device bytes (0: unknown)}.  out (out_cap >= 16 words):
+ *   [0] engine: 0 megakernel, 1 wavefront, 2 field pass
+ *   [1] the word debug counter 15 reads after the render (which kernel runs)
+ *   [2] compact pixels (padding of partial 8x8 tiles included)
+ *   [3] chunk: samples per pixel of a launch      [4] launches
+ *   [5] waves per SIMD   [6] Sobol dimensions staged in LDS   [7] direction-number nibbles
+ *   [8] scene in LDS | scan << 1 | start queue << 2 | gather mode << 3 | SFMT replay << 4
+ *   [9] gather mode's footprint offset H
+ *   [10] dynamic LDS bytes of the megakernel or field kernel (0: wavefront)
+ *   [11] the wavefront engine's path slots (0: another engine)      [12..15] zero
+ *   [16 + 3i ..] {samples per pixel, blocks, run shift} of launch i, while they fit out_cap
+ * On an error the render's code is returned and its text copied to msg. */
+int mtsgpu_plan_host(const mtsgpu_scene_desc *scene, const mtsgpu_render_params *params, uint32_t num_fields,
+                     int want_samples, const uint64_t dev[3], uint64_t *out, size_t out_cap, char *msg,
+                     size_t msg_cap);
 /* Diagnostics (tests): device arithmetic probe -- for each i, out[8i..8i+7] =
  * {a/b, sqrt|a|, sin a, cos a, acos(clamp a), atan2(a,b), exp(-|a|), a*b+a}
  * computed by the kernels' own routines; scene info = {nodes, prims, depth, CUs}. */

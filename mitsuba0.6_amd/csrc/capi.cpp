@@ -21,53 +21,12 @@
 #include "scene_build.h"
 #include "sfmt.h"
 #include "kdtree.h"
-
-hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool stats, hipStream_t stream);
-hipError_t mtsg_launch_gather(const MtsgLaunch &L, hipStream_t stream);
-hipError_t mtsg_launch_reduce(const MtsgLaunch &L, hipStream_t stream);
-hipError_t mtsg_launch_finalize(float *own, const double *spill, size_t n, hipStream_t stream);
-hipError_t mtsg_launch_arith_probe(const float *a, const float *b, float *out, int n, hipStream_t stream);
-hipError_t mtsg_launch_libm_probe(int fn, const float *a, const float *b, float *out, size_t n, uint32_t first,
-                                  hipStream_t s);
-hipError_t mtsg_launch_trace(const MtsgDeviceScene &S, const float *rays, uint32_t n, float *out, bool shadow,
-                             uint32_t stackDepth, int numCUs, hipStream_t stream);
-hipError_t mtsg_launch_trace_kd(const MtsgDeviceScene &S, const uint32_t *kdNodes, const uint32_t *kdIndices,
-                                const MtsgTri *kdTris, const float *rays, uint32_t n, float *out, bool shadow,
-                                int numCUs, hipStream_t stream);
-int mtsg_path_kernel_occupancy(const MtsgLaunch &L, int *blocksPerCU);
-int mtsg_path_variant(const MtsgLaunch &L);
-// the field pass (field_kernel.hip) and the multi-format develop (film_kernel.hip)
-hipError_t mtsg_launch_field(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream);
-int mtsg_field_occupancy(const MtsgLaunch &L, int *bpc);
-hipError_t mtsg_launch_develop_multi(const mtsgpu_develop_multi_params &P, const float *const *films, void *out,
-                                     int num_cus, hipStream_t s);
-hipError_t mtsg_launch_wf_shade(const MtsgLaunch &L, const MtsgWave &W, unsigned long long *part, int grid, int wk,
-                                bool ggx, bool instr, hipStream_t s);
-hipError_t mtsg_launch_wf_trace(const MtsgLaunch &L, const MtsgWave &W, unsigned long long *part, int grid,
-                                bool stats, hipStream_t s);
-hipError_t mtsg_launch_wf_flush(const unsigned long long *part, uint32_t blocks, unsigned long long *counters,
-                                hipStream_t s);
-int mtsg_wf_occupancy(const MtsgLaunch &L, int wk, bool ggx, int *shadeBpc, int *traceBpc);
-int mtsg_path_features(const MtsgLaunch &L);
-// the wavefront's trace kernel forms the whole hit record (MTSGPU_WF_HITREC=1; A/B in DESIGN.md 4)
-static bool wf_hitrec_on() {
-    const char *e = std::getenv("MTSGPU_WF_HITREC");
-    return e && e[0] == '1';
-}
-hipError_t mtsg_launch_sfmt_probe(uint32_t *w, unsigned long long *out, int n, hipStream_t s);
-hipError_t mtsg_launch_develop(const mtsgpu_develop_params &P, const float *film, void *out, int num_cus,
-                               hipStream_t s);
-int mtsg_develop_channels(int pixel_format);
-// ldrfilm develop (ldrfilm_kernel.hip)
-hipError_t mtsg_launch_develop_ldr(const mtsgpu_develop_ldr_params &P, const float *film, uint8_t *out, void *scratch,
-                                   int num_cus, hipStream_t s);
-size_t mtsg_develop_ldr_scratch(const mtsgpu_develop_ldr_params &P);
-size_t mtsg_develop_ldr_info_offset();
+#include "launchers.h"
+#include "render_plan.h"
 
 namespace {
 
 thread_local std::string g_create_error;
-constexpr size_t BLOCK_THREADS = 256;   // = BLOCK in path_kernel.hip
 
 struct DevBuf {
     void *p = nullptr;
@@ -97,9 +56,7 @@ struct mtsgpu_ctx {
     bool have_scene = false;
     HostScene host;
     MtsgDeviceScene dscene;
-    DevBuf scan_tris;   // k-grouped TriAccel records of scan-sized scenes
-    uint32_t scan_n[6] = {0, 0, 0, 0, 0, 0};   // as MtsgLaunch::scan_n: records | plane pairs << 16
-    uint32_t one_emitter = 0;   // the uploaded emitter CDF is {0.0f, 1.0f} bit for bit (MtsgLaunch::one_emitter)
+    DevBuf scan_tris;   // k-grouped TriAccel records of scan-sized scenes (their counts: host.launch.scan_n)
     DevBuf face_n;   // unit face normals per primitive (MtsgLaunch::face_n)
     DevBuf nodes, hnodes, tris, prim_vtx, dpdu, positions, normals, shapes, bsdfs, emitters, area_cdf, em_cdf, sobol;
     DevBuf env, env_texels, env_rows, env_cols, env_weights, env_grows, env_gcols;
@@ -123,18 +80,9 @@ struct mtsgpu_ctx {
     unsigned long long last_counters[16] = {};
 };
 
-// Every object that takes an MtsgLaunch by value reports the size it was compiled with.  A
-// library linked from objects of two layouts (a stale object after layout.h changed) would
-// hand its kernels a misread launch record: refuse to run instead.
-extern "C" {
-uint32_t mtsg_launch_bytes_path_kernel();
-uint32_t mtsg_launch_bytes_wf_kernel();
-uint32_t mtsg_launch_bytes_field_kernel();
-#define MTSG_BYTES_DECL(N) uint32_t mtsg_launch_bytes_path_f##N(); uint32_t mtsg_launch_bytes_wf_shade_f##N();
-MTSG_BYTES_DECL(0) MTSG_BYTES_DECL(1) MTSG_BYTES_DECL(2) MTSG_BYTES_DECL(3) MTSG_BYTES_DECL(6) MTSG_BYTES_DECL(7)
-#undef MTSG_BYTES_DECL
-}
-
+// Every object that takes an MtsgLaunch by value reports the size it was compiled with
+// (launchers.h).  A library linked from objects of two layouts (a stale object after layout.h
+// changed) would hand its kernels a misread launch record: refuse to run instead.
 namespace {
 
 // empty when every object agrees with this one on sizeof(MtsgLaunch), else what differs
@@ -246,53 +194,6 @@ int mtsgpu_create(int device, mtsgpu_ctx **out) {
     return MTSGPU_OK;
 }
 
-// tiny scenes: the TriAccel records grouped by projection axis and, within
-// an axis, planes normal to it (n_u = n_v = 0: the Cornell box's walls)
-// last, so the scan runs six branch-free loops, the aligned ones without
-// the numerator's and denominator's n_u/n_v terms (the closest hit and its
-// tie rule do not depend on the order the records are tested in).
-// Within a group, records that share their plane and vertex A -- the two
-// triangles of a quad triangulated as a fan -- come first, partners adjacent
-// at 2i and 2i+1 (np[group] pairs), the singles after them: a pair's t, hu
-// and hv are the same bits for both, so scan_pair forms them once.  Partners
-// have a_u and a_v bit-equal and n_u, n_v, n_d bit-equal (an aligned group:
-// n_d only, its loops never read n_u / n_v).  Bit-equality is an equivalence,
-// so pairing each record with the next unpaired equal one leaves at most one
-// single per plane.  MTSGPU_NO_SCAN_PAIRS: no pairs (A/B and tests).
-static void mtsg_scan_layout(const std::vector<MtsgTri> &tris, std::vector<MtsgTri> &g, uint32_t n[6], uint32_t np[6]) {
-    const bool pairs = !std::getenv("MTSGPU_NO_SCAN_PAIRS");
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    g.clear();
-    for (uint32_t k = 0; k < 3; ++k)
-        for (uint32_t al = 0; al < 2; ++al) {
-            std::vector<MtsgTri> m, singles;
-            for (const MtsgTri &t : tris)
-                if (t.k == k && (uint32_t)(t.n_u == 0.0f && t.n_v == 0.0f) == al) m.push_back(t);
-            std::vector<char> used(m.size(), 0);
-            uint32_t &cnt = np[2 * k + al];
-            cnt = 0;
-            for (size_t i = 0; i < m.size(); ++i) {
-                if (used[i]) continue;
-                size_t j = m.size();
-                if (pairs)
-                    for (j = i + 1; j < m.size(); ++j)
-                        if (!used[j] && bits(m[i].a_u) == bits(m[j].a_u) && bits(m[i].a_v) == bits(m[j].a_v) &&
-                            bits(m[i].n_d) == bits(m[j].n_d) &&
-                            (al || (bits(m[i].n_u) == bits(m[j].n_u) && bits(m[i].n_v) == bits(m[j].n_v))))
-                            break;
-                if (j < m.size()) {
-                    used[j] = 1;
-                    g.push_back(m[i]);
-                    g.push_back(m[j]);
-                    cnt++;
-                } else
-                    singles.push_back(m[i]);
-            }
-            g.insert(g.end(), singles.begin(), singles.end());
-            n[2 * k + al] = (uint32_t)m.size();
-        }
-}
-
 int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     if (!ctx || !scene) return MTSGPU_EINVAL;
     ctx->have_scene = false;
@@ -313,16 +214,11 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
         (e = upload(ctx->emitters, H.emitters, s)) != hipSuccess || (e = upload(ctx->area_cdf, H.area_cdf, s)) != hipSuccess ||
         (e = upload(ctx->em_cdf, H.em_cdf, s)) != hipSuccess || (e = upload(ctx->sobol, sobol_nibble_tables(), s)) != hipSuccess)
         return hip_fail(ctx, e, "scene upload");
-    // tiny scenes: the scan's grouped records (mtsg_scan_layout)
-    for (uint32_t &c : ctx->scan_n) c = 0;
-    if (H.tris.size() <= MTSG_SCAN_MAX && H.analytic.empty()) {
-        std::vector<MtsgTri> g;
-        uint32_t n[6], np[6];
-        mtsg_scan_layout(H.tris, g, n, np);
-        for (int k = 0; k < 6; ++k) ctx->scan_n[k] = n[k] | np[k] << 16;
-        if (g.empty()) g.push_back(MtsgTri{});
-        if ((e = upload(ctx->scan_tris, g, s)) != hipSuccess) return hip_fail(ctx, e, "scene upload");
-    }
+    // tiny scenes: the scan's grouped records (render_plan.cpp mtsg_scan_layout)
+    std::vector<MtsgTri> g;   // (lives until the sync below)
+    scene_scan_n(H, g, H.launch.scan_n);
+    if (!g.empty() && (e = upload(ctx->scan_tris, g, s)) != hipSuccess) return hip_fail(ctx, e, "scene upload");
+    H.launch.one_emitter = scene_one_emitter(H);
     const MtsgEnv *denv = nullptr;
     if (H.env.emitter >= 0) {
         if ((e = upload(ctx->env_texels, H.env_texels, s)) != hipSuccess || (e = upload(ctx->env_rows, H.env_cdf_rows, s)) != hipSuccess ||
@@ -365,22 +261,11 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     D.area_cdf = (const float *)ctx->area_cdf.p;
     D.em_cdf = (const float *)ctx->em_cdf.p;
     D.sobol = nullptr;
-    D.num_emitters = (uint32_t)H.emitters.size();
-    D.num_prims = (uint32_t)H.tris.size();
-    D.em_norm = H.em_norm;
+    scene_scalars(H, D);
     D.env = denv;
-    D.env_emitter = H.env.emitter;
     D.rtrans = H.rtrans.empty() ? nullptr : (const float *)ctx->rtrans.p;
     D.texcoords = H.texcoords.empty() ? nullptr : (const float *)ctx->texcoords.p;
     D.analytic = H.analytic.empty() ? nullptr : (const MtsgAnalytic *)ctx->analytic.p;
-    for (int a = 0; a < 3; ++a) { D.aabb_min[a] = H.aabb_min[a]; D.aabb_max[a] = H.aabb_max[a]; }
-    D.cam = H.cam;
-    // a launch constant of the scene: sampleReuse over the CDF {0, 1} is the identity (dpath.h shade)
-    {
-        uint32_t w[2] = {1u, 0u};
-        if (H.em_cdf.size() == 2) std::memcpy(w, H.em_cdf.data(), 8);
-        ctx->one_emitter = (H.emitters.size() == 1 && w[0] == 0u && w[1] == 0x3f800000u) ? 1u : 0u;
-    }
     ctx->have_scene = true;
     return MTSGPU_OK;
 }
@@ -404,51 +289,18 @@ int mtsgpu_film_border(int32_t rfilter, float rfilter_param) {
     return f.border;
 }
 
-// The wavefront engine's launch plan: the shade kinds the scene's shapes can
-// reach (the MISS kind always), each kernel's grid, the trace grid, the slots
-struct WfPlan {
-    bool kinds[MTSG_WK_KINDS] = {};
-    bool ggx[MTSG_WK_KINDS] = {};
-    int shadeGrid[MTSG_WK_KINDS] = {};
-    int traceGrid = 0;
-    uint32_t slots = 0;
-    bool hitrec = false;   // wf_trace forms the hit records (MtsgWave::hitrec)
-};
-
 // The wavefront engine for one chunk of samples (wf_kernel.hip): the MISS
 // kernel starts every slot's first path, then bounce after bounce the shade
 // kernel of each kind, then the trace kernel, until no path slot is live.  The
 // live count of every POLL-th bounce is read back asynchronously; the host
 // stays at most LAG polls ahead of the GPU, so the queues never drain and the
 // overshoot (empty bounces) stays small.
-// Entries per region of the wavefront queues.  A kernel's block b appends to
-// region b % R, at most BLOCK entries per block.  Ray queues are filled by the
-// shade kernels, one per kind over n_k <= slots entries in all: a region gets at
-// most sum_k ceil(ceil(n_k / BLOCK) / R) <= ceil((slots / BLOCK + K) / R) + K
-// blocks.  A kind queue gets the trace kernel's closest-hit entries (its first
-// nc <= slots entries: ceil((slots / BLOCK + 1) / R) + 1 blocks per region), and
-// the miss queue the shade kernels' appends as well.  Round 4 sized every
-// region for all slots: 8x the ray-queue bytes that can be live.
-static void wf_caps(size_t slots, size_t &capRay, size_t &capCls) {
-    const size_t B = BLOCK_THREADS, R = MTSG_WF_REGIONS, K = MTSG_WK_KINDS, nb = (slots + B - 1) / B;
-    const size_t shade = (nb + K + R - 1) / R + K, trace = (nb + 1 + R - 1) / R + 1;
-    capRay = std::min(slots, B * shade);
-    capCls = std::min(slots, B * (shade + trace));
-}
-
 static int wf_render_chunk(mtsgpu_ctx *ctx, const MtsgLaunch &L, bool instr, bool stats, hipStream_t stream,
                            const WfPlan &plan, const volatile int *cancel) {
     hipError_t e;
-    const uint32_t slots = plan.slots;
-    const size_t R = MTSG_WF_REGIONS;
-    size_t cap, capCls;
-    wf_caps(slots, cap, capCls);
-    // the shade kernels' launch record: their blocks are short-lived (one queue entry
-    // per thread), so the Sobol dimensions they stage in LDS are a per-block cost;
-    // MTSGPU_WF_SHADE_LDS_DIMS caps them (0: every dimension from HBM/L2)
-    MtsgLaunch Ls = L;
-    if (const char *env = std::getenv("MTSGPU_WF_SHADE_LDS_DIMS"))
-        Ls.lds_dims = std::min<uint32_t>(Ls.lds_dims, (uint32_t)std::strtoul(env, nullptr, 10));
+    const size_t R = MTSG_WF_REGIONS, cap = plan.cap, capCls = plan.capCls;
+    MtsgLaunch Ls = L;   // the shade kernels' launch record (plan_wavefront)
+    Ls.lds_dims = plan.shadeLdsDims;
     MtsgWave W;
     std::memset(&W, 0, sizeof W);
     W.state = (float4 *)ctx->wf_state.p;
@@ -463,17 +315,16 @@ static int wf_render_chunk(mtsgpu_ctx *ctx, const MtsgLaunch &L, bool instr, boo
     W.live = (uint32_t *)ctx->wf_live.p;
     W.ovf = (uint2 *)ctx->wf_ovf.p;
     W.shape_kind = (const uint32_t *)ctx->wf_kind.p;
-    W.slots = slots;
+    W.slots = plan.slots;
     W.cap = (uint32_t)cap;
     W.cap_cls = (uint32_t)capCls;
-    W.ovf_depth = L.stack_depth > MTSG_WF_LDS_STACK ? L.stack_depth - MTSG_WF_LDS_STACK : 0;
+    W.ovf_depth = (uint32_t)plan.ovfDepth;
     if (plan.hitrec) {
         W.hitrec = (float4 *)ctx->wf_hitrec.p;
-        W.hitrec_uv = (mtsg_path_features(L) & MTSG_FEAT_EXT) ? 1u : 0u;
+        W.hitrec_uv = plan.hitrecUv ? 1u : 0u;
     }
     unsigned long long *part = (unsigned long long *)ctx->wf_part.p;
-    int partBlocks = plan.traceGrid;
-    for (int k = 0; k < MTSG_WK_KINDS; ++k) partBlocks = std::max(partBlocks, plan.shadeGrid[k]);
+    const int partBlocks = plan.partBlocks;
     if ((e = hipMemsetAsync(ctx->wf_cnt.p, 0, (size_t)2 * MTSG_WF_QUEUES * R * 4, stream)) != hipSuccess ||
         (e = hipMemsetAsync(ctx->wf_live.p, 0, 2 * 4, stream)) != hipSuccess ||
         (e = hipMemsetAsync(part, 0, (size_t)partBlocks * 16 * 8, stream)) != hipSuccess)
@@ -517,586 +368,215 @@ static int wf_render_chunk(mtsgpu_ctx *ctx, const MtsgLaunch &L, bool instr, boo
     return MTSGPU_OK;
 }
 
-// shape -> shade kind (wf_kernel.hip) from the shape's BSDF type; per kind,
-// whether every BSDF of that kind uses the GGX distribution
-static void wf_kinds(const HostScene &H, std::vector<uint32_t> &shapeKind, WfPlan &plan) {
-    bool any[MTSG_WK_KINDS] = {}, nonGgx[MTSG_WK_KINDS] = {};
-    shapeKind.assign(std::max<size_t>(1, H.shapes.size()), (uint32_t)MTSG_WK_GEN);
-    for (size_t i = 0; i < H.shapes.size(); ++i) {
-        const MtsgBsdf &b = H.bsdfs[H.shapes[i].bsdf];
-        int k = MTSG_WK_GEN;
-        switch (b.type) {
-            case MTSGPU_BSDF_DIFFUSE: k = MTSG_WK_DIFF; break;
-            case MTSGPU_BSDF_ROUGHCONDUCTOR: k = MTSG_WK_RC; break;
-            case MTSGPU_BSDF_ROUGHDIELECTRIC: k = MTSG_WK_RD; break;
-            case MTSGPU_BSDF_ROUGHPLASTIC: k = MTSG_WK_RP; break;
-            default: break;
-        }
-        if (std::getenv("MTSGPU_WF_GENERIC")) k = MTSG_WK_GEN;   // A/B: every hit through the generic kernel
-        shapeKind[i] = (uint32_t)k;
-        any[k] = true;
-        if (b.distr != MTSGPU_DISTR_GGX) nonGgx[k] = true;
-    }
-    for (int k = 0; k < MTSG_WK_KINDS; ++k) {
-        plan.kinds[k] = any[k] || k == MTSG_WK_MISS;
-        plan.ggx[k] = any[k] && !nonGgx[k];
-    }
-}
-
 // ---------------------------------------------------------------------------
-// The `independent` sampler replay (MTSGPU_SAMPLER_SFMT_*): stream seeding and
-// the reference's render order
+// A render: what was asked (mtsgpu_render_params, a field list), what will be launched
+// (render_plan.h: no HIP call), and launching it: render_impl and its stages below
 // ---------------------------------------------------------------------------
-static void sfmt_period_certification(uint32_t *w) {   // random.cpp:322-347
-    const uint32_t parity[4] = {0x00000001u, 0x00000000u, 0x00000000u, 0x13c9e684u};
-    uint32_t inner = 0;
-    for (int i = 0; i < 4; ++i) inner ^= w[i] & parity[i];
-    for (int i = 16; i > 0; i >>= 1) inner ^= inner >> i;
-    if (inner & 1) return;
-    for (int i = 0; i < 4; ++i)
-        for (uint32_t work = 1, j = 0; j < 32; ++j, work <<= 1)
-            if (work & parity[i]) { w[i] ^= work; return; }
-}
-
-static void mtsg_sfmt_seed(uint32_t *w, uint64_t seed) {   // init_gen_rand (random.cpp:397-406)
-    uint64_t v = seed;
-    w[0] = (uint32_t)v;
-    w[1] = (uint32_t)(v >> 32);
-    for (int i = 1; i < MTSG_SFMT_N64; ++i) {
-        v = 6364136223846793005ull * (v ^ (v >> 62)) + (uint64_t)i;
-        w[2 * i] = (uint32_t)v;
-        w[2 * i + 1] = (uint32_t)(v >> 32);
-    }
-    w[MTSG_SFMT_N32] = MTSG_SFMT_N32;
-    sfmt_period_certification(w);
-}
-
-// Random(Random *parent): init_by_array over 312 of the parent's outputs as
-// 624 little-endian words (random.cpp:408-471, 528-548)
-static void mtsg_sfmt_clone(uint32_t *w, uint32_t *parent) {
-    uint32_t key[MTSG_SFMT_N32];
-    for (int i = 0; i < MTSG_SFMT_N64; ++i) {
-        const uint64_t v = sfmt_next_ulong(parent);
-        key[2 * i] = (uint32_t)v;
-        key[2 * i + 1] = (uint32_t)(v >> 32);
-    }
-    const int n = MTSG_SFMT_N32, lag = 11, mid = (n - lag) / 2, len = MTSG_SFMT_N32;
-    auto f1 = [](uint32_t x) { return (x ^ (x >> 27)) * 1664525u; };
-    auto f2 = [](uint32_t x) { return (x ^ (x >> 27)) * 1566083941u; };
-    std::memset(w, 0x8b, MTSG_SFMT_N32 * 4);
-    int count = std::max(len + 1, n);
-    uint32_t r = f1(w[0] ^ w[mid] ^ w[n - 1]);
-    w[mid] += r;
-    r += (uint32_t)len;
-    w[mid + lag] += r;
-    w[0] = r;
-    --count;
-    int i = 1, j = 0;
-    for (; j < count && j < len; ++j, i = (i + 1) % n) {
-        r = f1(w[i] ^ w[(i + mid) % n] ^ w[(i + n - 1) % n]);
-        w[(i + mid) % n] += r;
-        r += key[j] + (uint32_t)i;
-        w[(i + mid + lag) % n] += r;
-        w[i] = r;
-    }
-    for (; j < count; ++j, i = (i + 1) % n) {
-        r = f1(w[i] ^ w[(i + mid) % n] ^ w[(i + n - 1) % n]);
-        w[(i + mid) % n] += r;
-        r += (uint32_t)i;
-        w[(i + mid + lag) % n] += r;
-        w[i] = r;
-    }
-    for (j = 0; j < n; ++j, i = (i + 1) % n) {
-        r = f2(w[i] + w[(i + mid) % n] + w[(i + n - 1) % n]);
-        w[(i + mid) % n] ^= r;
-        r -= (uint32_t)i;
-        w[(i + mid + lag) % n] ^= r;
-        w[i] = r;
-    }
-    w[MTSG_SFMT_N32] = MTSG_SFMT_N32;
-    sfmt_period_certification(w);
-}
-
-namespace {
-// HilbertCurve2D<uint8_t>::generate (core/sfcurve.h): ENorth 0, EEast 1, ESouth 2, EWest 3
-void hilbert(int order, int front, int right, int back, int left, uint8_t pos[2], uint8_t w, uint8_t h, uint32_t bx,
-             uint32_t by, std::vector<uint32_t> &out) {
-    if (order == 0) {
-        if (pos[0] < w && pos[1] < h) out.push_back((bx + pos[0]) | ((by + pos[1]) << 16));
-        return;
-    }
-    auto move = [&](int d) {
-        if (d == 0) pos[1]--; else if (d == 1) pos[0]++; else if (d == 2) pos[1]++; else pos[0]--;
-    };
-    hilbert(order - 1, left, back, right, front, pos, w, h, bx, by, out); move(right);
-    hilbert(order - 1, front, right, back, left, pos, w, h, bx, by, out); move(back);
-    hilbert(order - 1, front, right, back, left, pos, w, h, bx, by, out); move(left);
-    hilbert(order - 1, right, front, left, back, pos, w, h, bx, by, out);
-}
-}  // namespace
-
-// the crop's pixels (x | y << 16, crop-relative) in the reference's order:
-// BlockedImageProcess's spiral (imageproc.cpp:28-80), HilbertCurve2D per block
-// (renderproc.cpp:79-81); blockStart: first pixel of each block, then the count
-static void mtsg_render_order(uint32_t width, uint32_t height, uint32_t bs, std::vector<uint32_t> &order,
-                       std::vector<uint32_t> &blockStart) {
-    const int nbx = (int)std::ceil((float)width / (float)bs), nby = (int)std::ceil((float)height / (float)bs);
-    const int total = nbx * nby;
-    int cx = nbx / 2, cy = nby / 2, dir = 0 /* ERight */, stepsLeft = 1, numSteps = 1;
-    const float invLog2 = 1.0f / (float)std::log((double)2.0f);   // math::fastlog (math.h:193-195)
-    order.clear();
-    blockStart.clear();
-    for (int b = 0; b < total; ++b) {
-        const int bw = std::min<int>((int)width - cx * (int)bs, (int)bs), bh = std::min<int>((int)height - cy * (int)bs, (int)bs);
-        blockStart.push_back((uint32_t)order.size());
-        const int order2 = (int)std::ceil(invLog2 * (float)std::log((double)(float)std::max(bw, bh)));
-        uint8_t pos[2] = {0, 0};
-        hilbert(order2, 0, 1, 2, 3, pos, (uint8_t)bw, (uint8_t)bh, (uint32_t)(cx * (int)bs), (uint32_t)(cy * (int)bs),
-                order);
-        if (b + 1 == total) break;
-        do {
-            if (dir == 0) ++cx; else if (dir == 1) ++cy; else if (dir == 2) --cx; else --cy;
-            if (--stepsLeft == 0) {
-                dir = (dir + 1) % 4;
-                if (dir == 2 || dir == 0) ++numSteps;   // ELeft, ERight
-                stepsLeft = numSteps;
-            }
-        } while (cx < 0 || cy < 0 || cx >= nbx || cy >= nby);
-    }
-    blockStart.push_back((uint32_t)order.size());
-}
-
-// megakernel sample runs (dmega.h): a lane renders 2^s consecutive samples of one pixel, so
-// its wave keeps the same 64 pixels for 2^s paths.  Large scenes: the longest runs that leave
-// every lane MTSG_MIN_RUNS of them (full frame: C3 s = 4 +13%, C5 s = 5 +14% over s = 0; longer
-// runs leave a tail, profiles/r06_rounds/).  Tiny LDS scenes gain nothing: pairs, whose box
-// records share a 32 B sector (film_slot).  MTSGPU_ROUND_SHIFT=s overrides (A/B)
-static uint32_t run_shift(const MtsgLaunch &L, uint64_t lanes) {
-    if (const char *env = std::getenv("MTSGPU_ROUND_SHIFT")) return (uint32_t)std::min(6, std::max(0, std::atoi(env)));
-    uint32_t s = L.scene_lds ? 1u : 6u;
-    const uint64_t perLane = L.num_items / std::max<uint64_t>(1, lanes);
-    while (s > 0 && ((1u << s) > L.chunk_spp || (perLane >> s) < MTSG_MIN_RUNS)) --s;
-    return s;
-}
-
-// the window's work decomposition: compact rows (interleave) x columns in 8x8 tiles, or
-// (tile shards) every row_stride-th 8x8 tile of the window; with the reciprocals the
-// kernels divide by (layout.h pixel_of)
-static void launch_geometry(MtsgLaunch &L, uint32_t x0, uint32_t y0, uint32_t width, uint32_t height, uint32_t row_block,
-                            uint32_t row_stride, uint32_t row_phase, bool tile_shard) {
-    L.x0 = x0; L.y0 = y0; L.width = width; L.height = height;
-    L.row_block = row_block ? row_block : 1;
-    L.row_stride = row_stride ? row_stride : 1;
-    L.row_phase = row_phase % L.row_stride;
-    L.tile_shard = tile_shard ? 1u : 0u;
-    L.tiles_x = (width + 7) / 8;
-    if (L.tile_shard) {
-        const uint64_t tiles = (uint64_t)L.tiles_x * ((height + 7) / 8);
-        L.num_pixels = (uint32_t)((tiles + L.row_stride - 1) / L.row_stride * 64);
-    } else {
-        const uint32_t rowsCompact =
-            ((height + L.row_block - 1) / L.row_block + L.row_stride - 1) / L.row_stride * L.row_block;
-        const uint32_t tilesY = (rowsCompact + 7) / 8;
-        L.num_pixels = L.tiles_x * tilesY * 64;
-    }
-    mtsg_launch_index(L, 0);   // the reciprocals; the megakernel's grid is known per chunk (render_impl)
-}
-
 // FJ: the field pass (mtsgpu_render_fields) -- the same window, sampler, filter, sharding and
 // film machinery with field_kernel in place of the integrator's kernel; film_host / film_dev
 // then hold FJ->n consecutive films and samples_host records of 4 + 3 * FJ->n floats
 struct FieldJob { const mtsgpu_field_desc *fields; uint32_t n; };
-static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *film_host, float *film_dev,
-                       float *samples_host, hipStream_t stream, mtsgpu_stats *stats, const FieldJob *FJ = nullptr) {
-    if (!ctx || !P) return MTSGPU_EINVAL;
-    if (!ctx->have_scene) return fail(ctx, MTSGPU_ESTATE, "render called before a successful upload_scene");
-    if (!launch_layout_error().empty()) return fail(ctx, MTSGPU_ESTATE, launch_layout_error());
-    if (P->spp == 0) return fail(ctx, MTSGPU_EINVAL, "sampleCount must be positive");
-    const uint32_t nFilms = FJ ? FJ->n : 1u;   // (the integrator fields of P are ignored by the field pass)
-    const bool pathLike = !FJ && (P->integrator == MTSGPU_INTEGRATOR_PATH || P->integrator == MTSGPU_INTEGRATOR_VOLPATH);
-    if (pathLike && P->rr_depth <= 0)
-        return fail(ctx, MTSGPU_EINVAL, "'rrDepth' must be set to a value greater than zero!");
-    if (pathLike && P->max_depth <= 0 && P->max_depth != -1)
-        return fail(ctx, MTSGPU_EINVAL, "'maxDepth' must be set to -1 (infinite) or a value greater than zero!");
-    const HostScene &H = ctx->host;
-    if ((uint64_t)P->x0 + P->width > H.film_w || (uint64_t)P->y0 + P->height > H.film_h)
-        return fail(ctx, MTSGPU_EINVAL, "render window exceeds the film");
-    if (P->cancel && *P->cancel) return fail(ctx, MTSGPU_ECANCEL, "cancelled");
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    if (!stream) stream = ctx->stream;
 
-    MtsgLaunch L;
-    std::memset(&L, 0, sizeof L);
-    L.scene = ctx->dscene;
-    std::string err;
-    if (mtsg_configure_filter(P->rfilter, P->rfilter_param, L.filter, err)) return fail(ctx, MTSGPU_EINVAL, err);
-    // SobolSampler::setFilmResolution(cropSize, bucketed = true) (sobol.cpp:147-158)
-    // the render window is the film's crop window: cropSize drives the sampler
-    // (Integrator::configureSampler, integrator.cpp:37-41)
-    const uint32_t mx = std::max(P->width, P->height);
-    uint32_t r = mx - 1;
-    r |= r >> 1; r |= r >> 2; r |= r >> 4; r |= r >> 8; r |= r >> 16; r += 1;
-    uint32_t m = 0;
-    while ((1u << m) < r) ++m;
-    L.resolution = (float)r;
-    L.diff_scale = 1.0f / std::sqrt((float)P->spp);   // integrator.cpp:144-145
-    mtsg_sobol_lookup_table(m, L.lut);
-    uint64_t scr = P->scramble;
-    if (scr) scr = mtsg_sample_tea((uint32_t)scr, (uint32_t)(scr >> 32), 4);   // sobol.cpp:93-101
-    L.scramble = (uint32_t)scr;
-    L.scramble64 = scr;
-    L.spp = P->spp;
-    L.max_depth = P->max_depth;
-    L.rr_depth = P->rr_depth;
-    L.strict_normals = P->strict_normals;
-    L.hide_emitters = P->hide_emitters;
-    L.has_alpha = FJ ? 1 : P->has_alpha;
-    L.film_w = (int)H.film_w;
-    L.film_h = (int)H.film_h;
-    L.fw = (int)H.film_w + 2 * L.filter.border;
-    L.fh = (int)H.film_h + 2 * L.filter.border;
-    launch_geometry(L, P->x0, P->y0, P->width, P->height, P->row_block, P->row_stride, P->row_phase,
-                    (P->flags & MTSGPU_FLAG_TILE_SHARD) != 0);
-    L.one_emitter = std::getenv("MTSGPU_NO_ONE_EMITTER") ? 0u : ctx->one_emitter;
-    L.face_n = (const float *)ctx->face_n.p;
-    // Sobol index width: frame << 2m | 2m bits (sobolseq.h:93-125); 52 columns per dimension
-    // the direct integrator's 2D sample arrays index the Sobol sequence at spp x count
-    const bool direct = !FJ && P->integrator == MTSGPU_INTEGRATOR_DIRECT;
-    if (!pathLike && !direct && !FJ) return fail(ctx, MTSGPU_EINVAL, "unknown integrator");
-    if (direct && P->emitter_samples + P->bsdf_samples == 0)
-        return fail(ctx, MTSGPU_EINVAL, "direct: emitterSamples + bsdfSamples must be positive");
-    if (P->sampler < MTSGPU_SAMPLER_SOBOL || P->sampler > MTSGPU_SAMPLER_SFMT_BLOCKS)
-        return fail(ctx, MTSGPU_EINVAL, "unknown sampler");
-    const bool replay = P->sampler == MTSGPU_SAMPLER_SFMT_REPLAY || P->sampler == MTSGPU_SAMPLER_SFMT_BLOCKS;
-    if (replay && FJ)
-        return fail(ctx, MTSGPU_EINVAL, "field pass: the SFMT replay samplers' draw positions depend on how many numbers the "
-                                        "radiance integrator consumed; a separate pass cannot reproduce the sample positions");
-    if (replay && (!pathLike || L.row_stride > 1 || P->width > 65535 || P->height > 65535))
-        return fail(ctx, MTSGPU_EINVAL, "SFMT replay: path/volpath over a whole crop window (no row shards)");
-    L.sampler = (uint32_t)P->sampler;
-    const uint64_t perSampleIdx = direct ? std::max<uint64_t>(1, std::max(P->emitter_samples, P->bsdf_samples)) : 1;
-    uint32_t sppBits = 0;
-    while ((1ull << sppBits) < (uint64_t)P->spp * perSampleIdx) ++sppBits;
-    const uint32_t indexBits = (m > 1 ? 2 * m : 0) + sppBits;
-    if (L.sampler == MTSGPU_SAMPLER_SOBOL && indexBits > 52)
-        return fail(ctx, MTSGPU_EINVAL, "sample index exceeds the 52-bit Sobol direction numbers");
-    // independent streams are keyed by (x, y, sample): 16 + 16 + 32 bits
-    if (L.sampler == MTSGPU_SAMPLER_INDEPENDENT && (H.film_w > 65536 || H.film_h > 65536 ||
-                                                   (uint64_t)P->spp * perSampleIdx > 0xFFFFFFFFull))
-        return fail(ctx, MTSGPU_EINVAL, "independent sampler: film or sample count too large for the stream key");
-    L.nibbles = indexBits <= 32 ? 8 : MTSG_NIBBLES;
-    L.lds_dims = 32;
-    L.sobol_nib = (const uint32_t *)ctx->sobol.p;
-    L.stack_depth = H.bvh_depth + 2;
-    L.num_nodes = (uint32_t)H.nodes.size();
-    // small scenes: stage the whole BVH + TriAccel array in LDS (<= 32 KiB)
-    L.num_verts = (uint32_t)(H.positions.size() / 3);
-    L.num_shapes = (uint32_t)H.shapes.size();
-    const size_t sceneBytes = H.nodes.size() * sizeof(MtsgNode) + H.tris.size() * sizeof(MtsgTri) +
-                              H.prim_vtx.size() * 4 + H.dpdu.size() * 4 + H.face_n.size() * 4 + H.positions.size() * 4 +
-                              H.normals.size() * 4 + H.shapes.size() * sizeof(MtsgShape);
-    L.scene_lds = (sceneBytes <= (32u << 10) && !std::getenv("MTSGPU_NO_SCENE_LDS")) ? 1u : 0u;
-    L.scan = (L.scene_lds && H.tris.size() <= MTSG_SCAN_MAX && H.analytic.empty() && !std::getenv("MTSGPU_NO_SCAN"))
-                 ? 1u : 0u;
-    L.scan_tris = (const MtsgTri *)ctx->scan_tris.p;
-    for (int k = 0; k < 6; ++k) L.scan_n[k] = ctx->scan_n[k];
-    // large scenes are latency-bound: run 4 waves/SIMD when 4 blocks' traversal
-    // stacks + look_up tables fit the 160 KiB LDS, with as many Sobol dims in
-    // LDS as the rest allows (the others are read through L1/L2)
-    L.ext = H.ext ? 1u : 0u;
-    L.ana = H.analytic.empty() ? 0u : 1u;
-    // gfx950 has 32 CUs per XCD; the hardware deals workgroups round-robin over
-    // the XCDs of the device (a CPX partition is one XCD: no remap).  A CU count
-    // that is not a multiple of 32 is not a whole-XCD partition: no remap either.
-    L.xcds = (ctx->num_cus % 32 == 0) ? (uint32_t)std::max(1, ctx->num_cus / 32) : 1u;
-    L.all_diffuse = std::getenv("MTSGPU_NO_DIFF_VARIANT") ? 0u : 1u;
-    for (const MtsgBsdf &b : H.bsdfs) L.all_diffuse &= b.type == MTSGPU_BSDF_DIFFUSE ? 1u : 0u;
-    // the scene's BSDF set, for the specialised megakernel variants (dbsdf.h BSet)
-    {
-        bool ggx = true, rc = false, rd = false;
-        for (const MtsgBsdf &b : H.bsdfs) {
-            const bool rough = b.type == MTSGPU_BSDF_ROUGHCONDUCTOR || b.type == MTSGPU_BSDF_ROUGHDIELECTRIC ||
-                               b.type == MTSGPU_BSDF_ROUGHPLASTIC;
-            if (rough && b.distr != MTSGPU_DISTR_GGX) ggx = false;
-            rc |= b.type == MTSGPU_BSDF_ROUGHCONDUCTOR;
-            rd |= b.type == MTSGPU_BSDF_ROUGHDIELECTRIC;
-        }
-        // the set variants traverse half-float node boxes (layout.h MtsgHNode): a
-        // scene beyond half range would get infinite (still exact, but useless) boxes
-        float extent = 0.0f;
-        for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs(H.aabb_min[a]), std::fabs(H.aabb_max[a])));
-        // (the set kernels are built without strictNormals: MTSG_FEAT_NOSTRICT)
-        L.bset = (std::getenv("MTSGPU_NO_BSDF_SETS") || !(extent < 32768.0f) || P->strict_normals) ? 0u
-                 : (ggx ? (uint32_t)MTSG_FEAT_GGX : 0u) | (rc ? 0u : (uint32_t)MTSG_FEAT_NORC) |
-                       (rd ? 0u : (uint32_t)MTSG_FEAT_NORD);
-        // envmap-only scenes (no area light, no constant emitter): the set kernels without
-        // refN (MTSG_FEAT_NOREFN, dpath.h PathShader::REFN)
-        bool envOnly = H.env.emitter >= 0 && !H.env.constant && !std::getenv("MTSGPU_NO_REFN_SPEC");
-        for (const MtsgEmitter &em : H.emitters) envOnly &= em.type == MTSG_EMITTER_ENVMAP;
-        if (L.bset && envOnly) L.bset |= (uint32_t)MTSG_FEAT_NOREFN;
-    }
-    // MIDirectIntegrator::configure / configureSampler (direct.cpp:128-143)
-    L.integrator = FJ ? (int32_t)MTSGPU_INTEGRATOR_PATH : P->integrator;
-    L.array_end = 5;
-    if (direct) {
-        const uint32_t nl = P->emitter_samples, nb = P->bsdf_samples;
-        const size_t sum = (size_t)nl + nb;
-        L.lum_samples = nl;
-        L.bsdf_samples = nb;
-        L.weight_bsdf = 1 / (float)nb;
-        L.weight_lum = 1 / (float)nl;
-        L.frac_bsdf = nb / (float)sum;
-        L.frac_lum = nl / (float)sum;
-        if (nl > 1) { L.lum_dim = L.array_end; L.array_end += 2; }
-        if (nb > 1) { L.bsdf_dim = L.array_end; L.array_end += 2; }
-    }
-    L.waves = 3;
-    if (!L.scene_lds) {
-        const size_t perBlock = (160u << 10) / 4;
-        const size_t fixed = ((size_t)L.stack_depth * 3 * BLOCK_THREADS + 1) / 2 * 4 + MTSG_LUT_WORDS * 4;
-        if (fixed < perBlock) {
-            L.waves = 4;
-            L.lds_dims = (uint32_t)std::min<size_t>(32, (perBlock - fixed) / ((size_t)L.nibbles * 16 * 4));
-        }
-    }
-    // the all-diffuse variant makes no calls: 4 waves/SIMD (128 VGPRs) beat 3 (C2 +8.3%)
-    // and 5 (-15%) (profiles/r02_ab_c2_waves4.log, r02_ab_c2_waves45.log)
-    if (L.scene_lds && L.all_diffuse) L.waves = 4;
-    if (const char *env = std::getenv("MTSGPU_WAVES")) {
-        const int w = std::atoi(env);
-        L.waves = w == 4 ? 4u : 3u;
-    }
-    L.round_shift = 0;   // set per chunk (run_shift)
-    // gather mode (film_gather, path_kernel.hip): filters whose footprint covers the
-    // neighbours (gaussian) -- every film pixel sums its neighbourhood's sample records in
-    // a fixed order instead of taking atomic splats.  H = the largest footprint offset from a
-    // sample's pixel: |x - px| <= floor(radius + 1/2) (film_splat's ceil/floor bounds)
-    L.gather = 0;
-    L.gather_h = 0;
-    if (P->rfilter != MTSGPU_RFILTER_BOX) {
-        const int H = std::max(L.filter.border, (int)std::floor(L.filter.radius + 0.5f));
-        if (H >= 1 && H <= MTSG_GATHER_HMAX && !std::getenv("MTSGPU_NO_GATHER")) {
-            L.gather = 1;
-            L.gather_h = (uint32_t)H;
-        }
-    }
-    if (const char *env = std::getenv("MTSGPU_SOBOL_LDS_DIMS"))
-        L.lds_dims = (uint32_t)std::min(1024l, std::max(0l, std::strtol(env, nullptr, 10)));
-    // own-pixel splat buffer [chunk][pixels] of float4; spp processed in chunks
-    // that fit the budget: a quarter of the device's free HBM, at most 32 GiB
-    // (C5's 1280x720x1024 splats, 15 GB, then run as one launch, one tail)
-    size_t budget = (size_t)8 << 30;
-    {
-        size_t freeB = 0, totalB = 0;
-        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && freeB / 4 > budget)
-            budget = std::min<size_t>(freeB / 4 + ctx->contrib.bytes, (size_t)32 << 30);
-    }
-    if (const char *env = std::getenv("MTSGPU_CONTRIB_BYTES")) budget = std::max<size_t>(std::strtoull(env, nullptr, 10), 1 << 20);
-    const size_t perSample = (size_t)L.num_pixels * (L.gather ? 32 : 16);   // one (gather mode: two) float4 per sample
-    // (the field pass keeps one record array per field under the same budget)
-    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(P->spp, budget / (perSample * nFilms)));
-    const size_t filmFloats = (size_t)L.fw * L.fh * 5;
-    const size_t fieldBytes = perSample * (chunk + (chunk & 1));   // one field's record array
-    if ((e = ctx->film_own.ensure(filmFloats * 4 * nFilms)) != hipSuccess ||
-        (e = ctx->film_spill.ensure(filmFloats * 8 * nFilms)) != hipSuccess ||
-        (e = ctx->counters.ensure(16 * 8)) != hipSuccess || (e = ctx->contrib.ensure(fieldBytes * nFilms)) != hipSuccess)
+namespace {
+
+// what the stages of one render share
+struct RenderRun {
+    mtsgpu_ctx *ctx;
+    const RenderPlan &plan;
+    hipStream_t stream;
+    MtsgLaunch L;        // the plan's launch record with the device pointers patched in
+    float *own;          // the film(s) on the device
+    MtsgFieldArgs FA;    // the field pass
+    WfPlan wf;           // the wavefront engine
+};
+
+// allocate and clear the film, record and counter buffers; the launch record's pointers
+int render_buffers(RenderRun &R, float *film_dev) {
+    mtsgpu_ctx *ctx = R.ctx;
+    const RenderPlan &p = R.plan;
+    hipStream_t stream = R.stream;
+    hipError_t e;
+    if ((e = ctx->film_own.ensure(p.filmFloats * 4 * p.films)) != hipSuccess ||
+        (e = ctx->film_spill.ensure(p.filmFloats * 8 * p.films)) != hipSuccess ||
+        (e = ctx->counters.ensure(16 * 8)) != hipSuccess || (e = ctx->contrib.ensure(p.fieldBytes * p.films)) != hipSuccess)
         return hip_fail(ctx, e, "film allocation");
-    float *own = film_dev ? film_dev : (float *)ctx->film_own.p;
-    const size_t recFloats = FJ ? 4 + 3 * (size_t)nFilms : (size_t)MTSGPU_SAMPLE_RECORD_FLOATS;
-    const size_t nsamp = samples_host ? (size_t)P->width * P->height * P->spp * recFloats : 0;
-    if (nsamp) {
-        if ((e = ctx->samples.ensure(nsamp * 4)) != hipSuccess) return hip_fail(ctx, e, "sample buffer");
-        if ((e = hipMemsetAsync(ctx->samples.p, 0, nsamp * 4, stream)) != hipSuccess) return hip_fail(ctx, e, "memset");
+    R.own = film_dev ? film_dev : (float *)ctx->film_own.p;
+    if (p.nsamp) {
+        if ((e = ctx->samples.ensure(p.nsamp * 4)) != hipSuccess) return hip_fail(ctx, e, "sample buffer");
+        if ((e = hipMemsetAsync(ctx->samples.p, 0, p.nsamp * 4, stream)) != hipSuccess) return hip_fail(ctx, e, "memset");
     }
-    if ((e = hipMemsetAsync(own, 0, filmFloats * 4 * nFilms, stream)) != hipSuccess ||
-        (e = hipMemsetAsync(ctx->film_spill.p, 0, filmFloats * 8 * nFilms, stream)) != hipSuccess ||
+    if ((e = hipMemsetAsync(R.own, 0, p.filmFloats * 4 * p.films, stream)) != hipSuccess ||
+        (e = hipMemsetAsync(ctx->film_spill.p, 0, p.filmFloats * 8 * p.films, stream)) != hipSuccess ||
         (e = hipMemsetAsync(ctx->counters.p, 0, 16 * 8, stream)) != hipSuccess)
         return hip_fail(ctx, e, "memset");
-    L.film_own = own;
+    MtsgLaunch &L = R.L;
+    L = p.L;
+    L.scene = ctx->dscene;
+    L.face_n = (const float *)ctx->face_n.p;
+    L.sobol_nib = (const uint32_t *)ctx->sobol.p;
+    L.scan_tris = (const MtsgTri *)ctx->scan_tris.p;
+    L.film_own = R.own;
     L.film_spill = (double *)ctx->film_spill.p;
-    L.samples = nsamp ? (float *)ctx->samples.p : nullptr;
+    L.samples = p.nsamp ? (float *)ctx->samples.p : nullptr;
     L.contrib = (float *)ctx->contrib.p;
-    unsigned long long *cnt = (unsigned long long *)ctx->counters.p;
-    L.counters = cnt;
+    L.counters = (unsigned long long *)ctx->counters.p;
+    return MTSGPU_OK;
+}
 
-    MtsgFieldArgs FA;
-    std::memset(&FA, 0, sizeof FA);
-    if (FJ) {
-        FA.num_fields = nFilms;
-        FA.record_floats = (uint32_t)recFloats;
-        FA.contrib_stride = fieldBytes / 4;
-        for (uint32_t f = 0; f < nFilms; ++f) {
-            FA.field[f] = FJ->fields[f].field;
-            for (int k = 0; k < 3; ++k) FA.undefined[f][k] = FJ->fields[f].undefined[k];
-            FA.spill[f] = L.film_spill + f * filmFloats;
-        }
-        // sensor->getWorldTransform()->eval(its.t).inverse() (field.cpp:137-139)
-        if (!mtsg_invert4(H.cam.to_world, FA.world_to_cam)) return fail(ctx, MTSGPU_EINVAL, "Singular matrix in Matrix::invert");
-        // its.primIndex counts within the mesh: the first global primitive of each shape
-        std::vector<uint32_t> &first = ctx->field_first_host;
-        first.assign(H.shapes.size(), 0u);
-        for (size_t p = H.prim_vtx.size() / 4; p-- > 0;) first[H.prim_vtx[4 * p + 3]] = (uint32_t)p;
-        if ((e = upload(ctx->field_first, first, stream)) != hipSuccess) return hip_fail(ctx, e, "field upload");
-        FA.shape_first = (const uint32_t *)ctx->field_first.p;
+// the field pass: field_kernel's second argument
+int render_field_args(RenderRun &R, const FieldJob &FJ) {
+    mtsgpu_ctx *ctx = R.ctx;
+    const RenderPlan &p = R.plan;
+    const HostScene &H = ctx->host;
+    MtsgFieldArgs &FA = R.FA;
+    FA.num_fields = p.films;
+    FA.record_floats = (uint32_t)p.recFloats;
+    FA.contrib_stride = p.fieldBytes / 4;
+    for (uint32_t f = 0; f < p.films; ++f) {
+        FA.field[f] = FJ.fields[f].field;
+        for (int k = 0; k < 3; ++k) FA.undefined[f][k] = FJ.fields[f].undefined[k];
+        FA.spill[f] = R.L.film_spill + f * p.filmFloats;
     }
-    int bpc = 0;
-    if (FJ) mtsg_field_occupancy(L, &bpc);
-    else mtsg_path_kernel_occupancy(L, &bpc);
-    if (bpc <= 0) bpc = 1;
-    const bool stats_mode = (P->flags & MTSGPU_FLAG_TRAVERSAL_STATS) != 0;
-    if (replay) {
-        // IndependentSampler's Random() = seed(5489); RenderJob clones it per worker in
-        // order (renderjob.cpp:58-66).  Units: one worker over all blocks, or one per block
-        if (chunk < P->spp) return fail(ctx, MTSGPU_EINVAL, "SFMT replay: sampleCount exceeds one chunk");
-        std::vector<uint32_t> order, blockStart;
-        mtsg_render_order(P->width, P->height, MTSG_BLOCK_SIZE, order, blockStart);
-        std::vector<uint32_t> unitStart;
-        if (P->sampler == MTSGPU_SAMPLER_SFMT_BLOCKS) unitStart = blockStart;
-        else unitStart = {0u, (uint32_t)order.size()};
-        const uint32_t units = (uint32_t)unitStart.size() - 1;
-        std::vector<uint32_t> streams((size_t)units * MTSG_SFMT_WORDS, 0u), master(MTSG_SFMT_WORDS, 0u);
-        mtsg_sfmt_seed(master.data(), 5489ull);
-        for (uint32_t u = 0; u < units; ++u) mtsg_sfmt_clone(streams.data() + (size_t)u * MTSG_SFMT_WORDS, master.data());
-        if ((e = upload(ctx->rp_order, order, stream)) != hipSuccess || (e = upload(ctx->rp_start, unitStart, stream)) != hipSuccess ||
-            (e = upload(ctx->rp_sfmt, streams, stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess)   // the host vectors go out of scope
-            return hip_fail(ctx, e, "replay upload");
-        L.replay = 1;
-        L.units = units;
-        L.order = (const uint32_t *)ctx->rp_order.p;
-        L.unit_start = (const uint32_t *)ctx->rp_start.p;
-        L.sfmt = (uint32_t *)ctx->rp_sfmt.p;
-    }
-    // execution engine (same per-sample results): the wavefront pipeline or the megakernel
-    bool wave = false;   // default: the megakernel (DESIGN.md 4 has the engine A/B)
-    if (const char *env = std::getenv("MTSGPU_ENGINE")) wave = pathLike && std::strcmp(env, "wavefront") == 0;
-    if (P->flags & MTSGPU_FLAG_WAVEFRONT) wave = pathLike;
-    if (P->flags & MTSGPU_FLAG_MEGAKERNEL) wave = false;
-    if (replay) wave = false;   // one lane per replay unit
-    if (FJ) wave = false;
-    if (!FJ && (P->flags & MTSGPU_FLAG_KDTREE)) {
-        // the reference's own kd-tree: the wavefront engine with wf_trace_kd
-        if (!pathLike || replay)
-            return fail(ctx, MTSGPU_EINVAL, "kd-tree traversal: path / volpath with the sobol or independent sampler");
-        if (P->flags & MTSGPU_FLAG_MEGAKERNEL) return fail(ctx, MTSGPU_EINVAL, "kd-tree traversal runs in the wavefront engine");
+    std::memcpy(FA.world_to_cam, p.world_to_cam, sizeof FA.world_to_cam);
+    // its.primIndex counts within the mesh: the first global primitive of each shape
+    std::vector<uint32_t> &first = ctx->field_first_host;
+    first.assign(H.shapes.size(), 0u);
+    for (size_t q = H.prim_vtx.size() / 4; q-- > 0;) first[H.prim_vtx[4 * q + 3]] = (uint32_t)q;
+    const hipError_t e = upload(ctx->field_first, first, R.stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "field upload");
+    FA.shape_first = (const uint32_t *)ctx->field_first.p;
+    return MTSGPU_OK;
+}
+
+// the SFMT replay: render order, unit starts and streams (replay_host.cpp)
+int render_replay(RenderRun &R, const mtsgpu_render_params &P) {
+    mtsgpu_ctx *ctx = R.ctx;
+    MtsgLaunch &L = R.L;
+    std::vector<uint32_t> order, unitStart, streams;
+    mtsg_replay_tables(P.width, P.height, P.sampler == MTSGPU_SAMPLER_SFMT_BLOCKS, order, unitStart, streams);
+    if (unitStart.size() - 1 != L.units) return fail(ctx, MTSGPU_ESTATE, "SFMT replay: the plan's units are not the render order's");
+    hipError_t e;
+    if ((e = upload(ctx->rp_order, order, R.stream)) != hipSuccess || (e = upload(ctx->rp_start, unitStart, R.stream)) != hipSuccess ||
+        (e = upload(ctx->rp_sfmt, streams, R.stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(R.stream)) != hipSuccess)   // the host vectors go out of scope
+        return hip_fail(ctx, e, "replay upload");
+    L.order = (const uint32_t *)ctx->rp_order.p;
+    L.unit_start = (const uint32_t *)ctx->rp_start.p;
+    L.sfmt = (uint32_t *)ctx->rp_sfmt.p;
+    return MTSGPU_OK;
+}
+
+// the wavefront engine: the kd-tree where wanted, the kernels' occupancy, the queues (plan_wavefront)
+int render_wavefront_buffers(RenderRun &R, const RenderKnobs &K) {
+    mtsgpu_ctx *ctx = R.ctx;
+    MtsgLaunch &L = R.L;
+    hipStream_t stream = R.stream;
+    hipError_t e;
+    if (R.plan.kdtree) {
         const int rc = ensure_kdtree(ctx);
         if (rc) return rc;
-        wave = true;
         L.kd_nodes = (const uint32_t *)ctx->kd_nodes.p;
         L.kd_indices = (const uint32_t *)ctx->kd_indices.p;
         L.kd_tris = (const MtsgTri *)ctx->kd_tris.p;
     }
-    WfPlan plan;
-    if (wave) {
-        std::vector<uint32_t> &shapeKind = ctx->wf_kind_host;   // kept alive for the async upload
-        wf_kinds(ctx->host, shapeKind, plan);
-        const size_t R = MTSG_WF_REGIONS;
-        for (int k = 0; k < MTSG_WK_KINDS; ++k) {
-            if (!plan.kinds[k]) continue;
-            int sb = 0, tb = 0;
-            mtsg_wf_occupancy(L, k, plan.ggx[k], &sb, &tb);
-            if (sb <= 0 || tb <= 0) return fail(ctx, MTSGPU_EHIP, "wavefront kernels do not fit the device");
-        }
-        // path slots: about 2M (MTSGPU_WF_SLOTS), whole blocks; the kernels run one queue
-        // entry per thread, so each grid covers the largest its queues can be (slots;
-        // 2 x slots for the trace kernel's two ray queues) and surplus blocks exit at once
-        uint64_t target = (uint64_t)1 << 21;
-        if (const char *env = std::getenv("MTSGPU_WF_SLOTS")) target = std::max<uint64_t>(1, std::strtoull(env, nullptr, 10));
-        const uint64_t items = (uint64_t)std::min(chunk, P->spp) * L.num_pixels;
-        target = std::min(target, items);
-        plan.slots = (uint32_t)((std::max<uint64_t>(1, target) + BLOCK_THREADS - 1) / BLOCK_THREADS * BLOCK_THREADS);
-        for (int k = 0; k < MTSG_WK_KINDS; ++k)
-            if (plan.kinds[k]) plan.shadeGrid[k] = (int)(plan.slots / BLOCK_THREADS);
-        plan.traceGrid = (int)(2 * (uint64_t)plan.slots / BLOCK_THREADS);
-        plan.hitrec = wf_hitrec_on();
-        const size_t slots = plan.slots;
-        size_t cap, capCls;
-        wf_caps(slots, cap, capCls);
-        const size_t ovfDepth = L.stack_depth > MTSG_WF_LDS_STACK ? L.stack_depth - MTSG_WF_LDS_STACK : 0;
-        int partBlocks = plan.traceGrid;
-        for (int k = 0; k < MTSG_WK_KINDS; ++k) partBlocks = std::max(partBlocks, plan.shadeGrid[k]);
-        if ((e = ctx->wf_state.ensure((size_t)MTSG_WF_STATE_VECS * slots * 16)) != hipSuccess ||
-            (e = ctx->wf_ray.ensure((size_t)2 * 2 * R * cap * 32)) != hipSuccess ||
-            (e = ctx->wf_rslot.ensure((size_t)2 * 2 * R * cap * 4)) != hipSuccess ||
-            (e = ctx->wf_cls.ensure((size_t)2 * MTSG_WK_KINDS * R * capCls * 4)) != hipSuccess ||
-            (e = ctx->wf_cnt.ensure((size_t)2 * MTSG_WF_QUEUES * R * 4)) != hipSuccess ||
-            (e = ctx->wf_hit.ensure(slots * 16)) != hipSuccess ||
-            (plan.hitrec && (e = ctx->wf_hitrec.ensure(slots * MTSG_WF_HIT_VECS * 16)) != hipSuccess) ||
-            (e = ctx->wf_occl.ensure(slots * 4)) != hipSuccess ||
-            (e = ctx->wf_live.ensure(2 * 4)) != hipSuccess ||
-            (e = ctx->wf_ovf.ensure((size_t)plan.traceGrid * BLOCK_THREADS * ovfDepth * 8)) != hipSuccess ||
-            (e = ctx->wf_part.ensure((size_t)partBlocks * 16 * 8)) != hipSuccess ||
-            (e = upload(ctx->wf_kind, shapeKind, stream)) != hipSuccess)
-            return hip_fail(ctx, e, "wavefront buffers");
-        if (!ctx->wf_live_host) {
-            if ((e = hipHostMalloc((void **)&ctx->wf_live_host, 8 * sizeof(uint32_t))) != hipSuccess)
-                return hip_fail(ctx, e, "wavefront pinned buffer");
-            for (hipEvent_t &ev : ctx->wf_ev)
-                if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return hip_fail(ctx, e, "event");
-        }
+    R.wf = plan_wavefront(R.plan, ctx->host, K);
+    const WfPlan &wf = R.wf;
+    for (int k = 0; k < MTSG_WK_KINDS; ++k) {
+        if (!wf.kinds[k]) continue;
+        int sb = 0, tb = 0;
+        mtsg_wf_occupancy(L, k, wf.ggx[k], &sb, &tb);
+        if (sb <= 0 || tb <= 0) return fail(ctx, MTSGPU_EHIP, "wavefront kernels do not fit the device");
     }
+    ctx->wf_kind_host = wf.shapeKind;   // kept alive for the async upload
+    const size_t Rg = MTSG_WF_REGIONS, slots = wf.slots;
+    if ((e = ctx->wf_state.ensure((size_t)MTSG_WF_STATE_VECS * slots * 16)) != hipSuccess ||
+        (e = ctx->wf_ray.ensure((size_t)2 * 2 * Rg * wf.cap * 32)) != hipSuccess ||
+        (e = ctx->wf_rslot.ensure((size_t)2 * 2 * Rg * wf.cap * 4)) != hipSuccess ||
+        (e = ctx->wf_cls.ensure((size_t)2 * MTSG_WK_KINDS * Rg * wf.capCls * 4)) != hipSuccess ||
+        (e = ctx->wf_cnt.ensure((size_t)2 * MTSG_WF_QUEUES * Rg * 4)) != hipSuccess ||
+        (e = ctx->wf_hit.ensure(slots * 16)) != hipSuccess ||
+        (wf.hitrec && (e = ctx->wf_hitrec.ensure(slots * MTSG_WF_HIT_VECS * 16)) != hipSuccess) ||
+        (e = ctx->wf_occl.ensure(slots * 4)) != hipSuccess ||
+        (e = ctx->wf_live.ensure(2 * 4)) != hipSuccess ||
+        (e = ctx->wf_ovf.ensure((size_t)wf.traceGrid * MTSG_BLOCK * wf.ovfDepth * 8)) != hipSuccess ||
+        (e = ctx->wf_part.ensure((size_t)wf.partBlocks * 16 * 8)) != hipSuccess ||
+        (e = upload(ctx->wf_kind, ctx->wf_kind_host, stream)) != hipSuccess)
+        return hip_fail(ctx, e, "wavefront buffers");
+    if (!ctx->wf_live_host) {
+        if ((e = hipHostMalloc((void **)&ctx->wf_live_host, 8 * sizeof(uint32_t))) != hipSuccess)
+            return hip_fail(ctx, e, "wavefront pinned buffer");
+        for (hipEvent_t &ev : ctx->wf_ev)
+            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return hip_fail(ctx, e, "event");
+    }
+    return MTSGPU_OK;
+}
+
+// the chunk loop: per launch of the plan the engine's kernels, then the film kernels;
+// launched: the loop's iterations (debug counter 8)
+int render_launches(RenderRun &R, const volatile int *cancel, unsigned long long &launched) {
+    mtsgpu_ctx *ctx = R.ctx;
+    const RenderPlan &p = R.plan;
+    MtsgLaunch &L = R.L;
+    hipStream_t stream = R.stream;
+    hipError_t e;
+    int bpc = 0;   // resident blocks per CU of the persistent kernel
+    if (p.engine == MTSG_ENGINE_FIELDS) mtsg_field_occupancy(L, &bpc);
+    else if (p.engine == MTSG_ENGINE_MEGAKERNEL) mtsg_path_kernel_occupancy(L, &bpc);
     if ((e = hipEventRecord(ctx->ev0, stream)) != hipSuccess) return hip_fail(ctx, e, "event");
-    unsigned long long launchedChunks = 0;   // (debug counter 8)
-    for (uint32_t j0 = 0; j0 < P->spp; j0 += chunk) {
-        if (P->cancel && *P->cancel) break;
-        ++launchedChunks;
+    launched = 0;
+    for (uint32_t j0 = 0; j0 < L.spp; j0 += p.chunk) {
+        if (cancel && *cancel) break;
+        ++launched;
+        const LaunchPlan lp = plan_launch(p, j0, bpc);
+        if (lp.err) return fail(ctx, MTSGPU_EINVAL, lp.err);
         L.j0 = j0;
-        L.chunk_spp = std::min(chunk, P->spp - j0);
-        L.num_items = (uint64_t)L.chunk_spp * L.num_pixels;
-        if (wave) {
-            const int rc = wf_render_chunk(ctx, L, nsamp != 0 || stats_mode, stats_mode, stream, plan, P->cancel);
+        L.chunk_spp = lp.chunk_spp;
+        L.num_items = lp.num_items;
+        if (p.engine == MTSG_ENGINE_WAVEFRONT) {
+            const int rc = wf_render_chunk(ctx, L, p.instr, p.stats_mode, stream, R.wf, cancel);
             if (rc != MTSGPU_OK) return rc;
         } else {
-            const uint64_t blocksNeeded = replay ? (L.units + 255) / 256 : (L.num_items + 255) / 256;
-            const int grid = (int)std::min<uint64_t>((uint64_t)ctx->num_cus * bpc, std::max<uint64_t>(1, blocksNeeded));
-            // the replay renders one unit per lane (its own SFMT stream): every unit needs a resident lane
-            if (replay && (uint64_t)grid * 256 < L.units)
-                return fail(ctx, MTSGPU_EINVAL, "SFMT replay: more 32x32 blocks than resident lanes (crop too large)");
-            L.round_shift = run_shift(L, (uint64_t)grid * BLOCK_THREADS);
-            mtsg_launch_index(L, (uint64_t)grid * BLOCK_THREADS);
-            if (FJ) {
-                if ((e = mtsg_launch_field(L, FA, grid, stream)) != hipSuccess) return hip_fail(ctx, e, "field kernel launch");
-            } else if ((e = mtsg_launch_path(L, grid, nsamp != 0, stats_mode, stream)) != hipSuccess) {
+            L.round_shift = lp.round_shift;
+            mtsg_launch_index(L, (uint64_t)lp.grid * MTSG_BLOCK);
+            if (p.engine == MTSG_ENGINE_FIELDS) {
+                if ((e = mtsg_launch_field(L, R.FA, lp.grid, stream)) != hipSuccess) return hip_fail(ctx, e, "field kernel launch");
+            } else if ((e = mtsg_launch_path(L, lp.grid, p.nsamp != 0, p.stats_mode, stream)) != hipSuccess) {
                 return hip_fail(ctx, e, "path kernel launch");
             }
         }
         // (the field pass: every field's record array into its own film, by the same kernels)
-        for (uint32_t f = 0; f < nFilms; ++f) {
+        for (uint32_t f = 0; f < p.films; ++f) {
             MtsgLaunch Lf = L;
-            Lf.contrib = L.contrib + f * (fieldBytes / 4);
-            Lf.film_own = own + f * filmFloats;
+            Lf.contrib = L.contrib + f * (p.fieldBytes / 4);
+            Lf.film_own = R.own + f * p.filmFloats;
             if ((e = Lf.gather ? mtsg_launch_gather(Lf, stream) : mtsg_launch_reduce(Lf, stream)) != hipSuccess)
                 return hip_fail(ctx, e, "film reduce launch");
         }
     }
     if ((e = hipEventRecord(ctx->ev1, stream)) != hipSuccess) return hip_fail(ctx, e, "event");
-    if ((e = mtsg_launch_finalize(own, L.film_spill, filmFloats * nFilms, stream)) != hipSuccess) return hip_fail(ctx, e, "finalize launch");
+    return MTSGPU_OK;
+}
+
+// finalize the film(s), read back, fill the stats, set debug counters 8 and 15
+int render_readback(RenderRun &R, float *film_host, float *samples_host, mtsgpu_stats *stats, unsigned long long launched) {
+    mtsgpu_ctx *ctx = R.ctx;
+    const RenderPlan &p = R.plan;
+    hipStream_t stream = R.stream;
+    hipError_t e;
+    if ((e = mtsg_launch_finalize(R.own, R.L.film_spill, p.filmFloats * p.films, stream)) != hipSuccess)
+        return hip_fail(ctx, e, "finalize launch");
     unsigned long long hc[16];
-    if ((e = hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, stream)) != hipSuccess) return hip_fail(ctx, e, "counters");
-    if (film_host && (e = hipMemcpyAsync(film_host, own, filmFloats * 4 * nFilms, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(hc, R.L.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) != hipSuccess) return hip_fail(ctx, e, "counters");
+    if (film_host && (e = hipMemcpyAsync(film_host, R.own, p.filmFloats * 4 * p.films, hipMemcpyDeviceToHost, stream)) != hipSuccess)
         return hip_fail(ctx, e, "film copy");
-    if (nsamp && (e = hipMemcpyAsync(samples_host, ctx->samples.p, nsamp * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+    if (p.nsamp && (e = hipMemcpyAsync(samples_host, ctx->samples.p, p.nsamp * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
         return hip_fail(ctx, e, "sample copy");
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(ctx, e, "path kernel");
     std::memcpy(ctx->last_counters, hc, sizeof hc);
     // counter 8: the launches the sample count was split into (the chunk loop's iterations)
-    ctx->last_counters[8] = launchedChunks;
-    // counter 15: which kernel ran -- for the megakernel path_kernel<INSTR, SCENE_LDS, FEAT, WAVES>:
-    // FEAT's low 8 bits | WAVES << 8 | SCENE_LDS << 12 | INSTR << 13 | (FEAT & NOSTRICT) << 14 (the
-    // set kernels' strictNormals-free build) | (FEAT & NOREFN) << 15; 1 << 16 for the wavefront engine
-    // (tests and A/B logs read it)
-    if (wave) {
-        ctx->last_counters[15] = 1ull << 16;
-    } else if (FJ) {   // field_kernel<SCENE_LDS, ..>: 1 << 17 | SCENE_LDS << 12
-        ctx->last_counters[15] = (1ull << 17) | ((unsigned long long)L.scene_lds << 12);
-    } else {
-        const int v = mtsg_path_variant(L);
-        ctx->last_counters[15] = (unsigned long long)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) |
-                                                      ((nsamp != 0 || stats_mode) ? 1 << 13 : 0) |
-                                                      ((v & MTSG_FEAT_NOSTRICT) ? 1 << 14 : 0) |
-                                                      ((v & MTSG_FEAT_NOREFN) ? 1 << 15 : 0));
-    }
+    ctx->last_counters[8] = launched;
+    // counter 15: which kernel ran (render_plan.cpp plan_variant_word)
+    ctx->last_counters[15] = plan_variant_word(p);
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     if (stats) {
@@ -1104,15 +584,47 @@ static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *fi
         stats->rays = hc[1];
         stats->shadow_rays = hc[2];
         stats->path_length_sum = hc[3];
-        stats->node_visits = stats_mode ? hc[4] : 0;
-        stats->tri_tests = stats_mode ? hc[5] : 0;
-        stats->hits = stats_mode ? hc[7] : 0;
-        stats->nee_samples = stats_mode ? hc[9] : 0;
-        stats->sobol_reads = stats_mode ? hc[10] : 0;
+        stats->node_visits = p.stats_mode ? hc[4] : 0;
+        stats->tri_tests = p.stats_mode ? hc[5] : 0;
+        stats->hits = p.stats_mode ? hc[7] : 0;
+        stats->nee_samples = p.stats_mode ? hc[9] : 0;
+        stats->sobol_reads = p.stats_mode ? hc[10] : 0;
         stats->kernel_ms = ms;
     }
     if (hc[6]) return fail(ctx, MTSGPU_EDIM, "Lookup dimension exceeds the direction number table size! You may have to "
                                              "reduce the 'maxDepth' parameter of your integrator.");
+    return MTSGPU_OK;
+}
+
+}  // namespace
+
+static int render_impl(mtsgpu_ctx *ctx, const mtsgpu_render_params *P, float *film_host, float *film_dev,
+                       float *samples_host, hipStream_t stream, mtsgpu_stats *stats, const FieldJob *FJ = nullptr) {
+    if (!ctx || !P) return MTSGPU_EINVAL;
+    if (!ctx->have_scene) return fail(ctx, MTSGPU_ESTATE, "render called before a successful upload_scene");
+    if (!launch_layout_error().empty()) return fail(ctx, MTSGPU_ESTATE, launch_layout_error());
+    const hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    // what the plan needs to know of the device, the environment once per render, the plan
+    DeviceFacts dev = {ctx->num_cus, 0, ctx->contrib.bytes};
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) dev.free_bytes = freeB;
+    const RenderKnobs K = read_knobs();
+    RenderPlan plan;
+    std::string err;
+    int rc = plan_render(ctx->host, *P, FJ ? FJ->n : 0u, samples_host != nullptr, dev, K, plan, err);
+    if (rc) return fail(ctx, rc, err);
+    if (P->cancel && *P->cancel) return fail(ctx, MTSGPU_ECANCEL, "cancelled");
+
+    RenderRun R = {ctx, plan, stream ? stream : ctx->stream};
+    std::memset(&R.FA, 0, sizeof R.FA);
+    unsigned long long launched = 0;
+    if ((rc = render_buffers(R, film_dev)) != MTSGPU_OK) return rc;
+    if (FJ && (rc = render_field_args(R, *FJ)) != MTSGPU_OK) return rc;
+    if (plan.replay && (rc = render_replay(R, *P)) != MTSGPU_OK) return rc;
+    if (plan.engine == MTSG_ENGINE_WAVEFRONT && (rc = render_wavefront_buffers(R, K)) != MTSGPU_OK) return rc;
+    if ((rc = render_launches(R, P->cancel, launched)) != MTSGPU_OK) return rc;
+    if ((rc = render_readback(R, film_host, samples_host, stats, launched)) != MTSGPU_OK) return rc;
     if (P->cancel && *P->cancel) return fail(ctx, MTSGPU_ECANCEL, "cancelled");
     return MTSGPU_OK;
 }
@@ -1507,7 +1019,8 @@ int mtsgpu_face_normals_host(const mtsgpu_scene_desc *scene, float *normals, flo
 }
 
 // geom = {x0, y0, width, height, row_block, row_stride, row_phase, tile_shard, chunk_spp,
-// round_shift, lanes}: the launch's index constants as render_impl forms them, then for each
+// round_shift, lanes}: the launch's index constants as a render forms them (render_plan.cpp
+// launch_geometry, layout.h mtsg_launch_index), then for each
 // (lane, round) the megakernel's own stepping (layout.h mtsg_run_init / mtsg_run_step, pixel_of)
 int mtsgpu_index_host(const uint32_t geom[11], const uint32_t *lane_round, size_t n, uint32_t *out, uint32_t info2[2]) {
     if (!geom || (n && (!lane_round || !out))) return MTSGPU_EINVAL;
@@ -1538,6 +1051,45 @@ int mtsgpu_index_host(const uint32_t geom[11], const uint32_t *lane_round, size_
     return MTSGPU_OK;
 }
 
+// The plan of a render without a device (include/mtsgpu.h has out[]'s layout): the scene
+// configured on the host, the environment read, then the functions render_impl runs
+int mtsgpu_plan_host(const mtsgpu_scene_desc *scene, const mtsgpu_render_params *params, uint32_t num_fields,
+                     int want_samples, const uint64_t dev[3], uint64_t *out, size_t out_cap, char *msg, size_t msg_cap) {
+    if (!scene || !params || !dev || !out || out_cap < 16 || num_fields > MTSGPU_MAX_FIELDS) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    int rc = mtsg_configure_scene(scene, H, err);
+    RenderPlan plan;
+    const RenderKnobs K = read_knobs();
+    if (!rc) {
+        std::vector<MtsgTri> g;
+        scene_scan_n(H, g, H.launch.scan_n);
+        H.launch.one_emitter = scene_one_emitter(H);
+        const DeviceFacts facts = {(int)dev[0], (size_t)dev[2], 0};
+        rc = plan_render(H, *params, num_fields, want_samples != 0, facts, K, plan, err);
+    }
+    const MtsgLaunch &L = plan.L;
+    const uint64_t launches = rc ? 0 : (L.spp + plan.chunk - 1) / plan.chunk;
+    for (uint64_t i = 0; !rc && i < launches; ++i) {
+        const LaunchPlan lp = plan_launch(plan, (uint32_t)(i * plan.chunk), dev[1] ? (int)dev[1] : (int)L.waves);
+        if (lp.err) { err = lp.err; rc = MTSGPU_EINVAL; break; }
+        if (16 + 3 * i + 3 > out_cap) continue;
+        out[16 + 3 * i] = lp.chunk_spp;
+        out[17 + 3 * i] = (uint64_t)lp.grid;
+        out[18 + 3 * i] = lp.round_shift;
+    }
+    if (msg && msg_cap) std::snprintf(msg, msg_cap, "%s", err.c_str());
+    if (rc) return rc;
+    const bool wave = plan.engine == MTSG_ENGINE_WAVEFRONT;
+    const uint64_t head[16] = {(uint64_t)plan.engine, plan_variant_word(plan), L.num_pixels, plan.chunk, launches, L.waves,
+                               L.lds_dims, L.nibbles,
+                               L.scene_lds | L.scan << 1 | (mtsg_path_start_queue(L) ? 4u : 0u) | L.gather << 3 | L.replay << 4,
+                               L.gather_h, wave ? 0 : mtsg_path_lds_bytes(L), wave ? plan_wavefront(plan, H, K).slots : 0u,
+                               0, 0, 0, 0};
+    std::memcpy(out, head, sizeof head);
+    return MTSGPU_OK;
+}
+
 // sobol::look_up for film resolution 2^m through the tables the kernels stage
 // (layout.h mtsg_lut_word, sobol_lookup_lds): out[i] = the index of sample j at pixel (px, py)
 int mtsgpu_lookup_host(uint32_t m, uint64_t scramble, const uint32_t *px_py_j, size_t n, uint64_t *out) {
@@ -1548,7 +1100,9 @@ int mtsgpu_lookup_host(uint32_t m, uint64_t scramble, const uint32_t *px_py_j, s
     for (uint32_t i = 0; i < MTSG_LUT_WORDS; ++i) tab[i] = mtsg_lut_word(lut, i);
     for (size_t i = 0; i < n; ++i) {
         const uint32_t j = px_py_j[3 * i + 2];
-        const uint32_t nibbles = ((uint64_t)j << (2 * m)) >> 32 ? MTSG_NIBBLES : 8;   // as render_impl: 8 while the index fits 32 bits
+        uint32_t indexBits = 0;   // of this sample's index, frame << 2m | 2m bits
+        while (indexBits < 64 && (((uint64_t)j << (2 * m)) >> indexBits)) ++indexBits;
+        const uint32_t nibbles = sobol_nibbles(indexBits);   // the planner's rule (render_plan.h)
         out[i] = sobol_lookup_lds(lut, (const uint32_t *)tab, nibbles, j, px_py_j[3 * i], px_py_j[3 * i + 1], scramble);
     }
     return MTSGPU_OK;

@@ -24,8 +24,7 @@
 //    (and the whole scene, with its triangles' unit face normals, for small ones).
 #pragma once
 #include "dpath.h"
-
-size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // path_kernel.hip
+#include "launchers.h"
 
 // tiny-scene kernels built without the start queue (-DMTSG_START_QUEUE=0) keep a pair's
 // first splat record in registers (PathShader::finish)
@@ -376,15 +375,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
 }
 
 
-// one megakernel variant: its launch and its resident blocks per CU
+// one megakernel variant, instrumented or not: the one place that names path_kernel<...>
+// (launch and occupancy query both take the pointer: path_f.hip, path_kernel.hip path_pick)
 template <bool SCENE_LDS, int FEAT, int WAVES>
-static void launch_path_w(const MtsgLaunch &L, int grid, bool instr, hipStream_t stream) {
-    const size_t lds = mtsg_path_lds_bytes(L);
-    if (instr) hipLaunchKernelGGL((path_kernel<true, SCENE_LDS, FEAT, WAVES>), dim3(grid), dim3(BLOCK), lds, stream, L);
-    else hipLaunchKernelGGL((path_kernel<false, SCENE_LDS, FEAT, WAVES>), dim3(grid), dim3(BLOCK), lds, stream, L);
-}
-template <bool SCENE_LDS, int FEAT, int WAVES>
-static int occupancy_w(const MtsgLaunch &L, int *bpc) {
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(bpc, path_kernel<false, SCENE_LDS, FEAT, WAVES>, BLOCK,
-                                                             mtsg_path_lds_bytes(L));
+static PathKernelFn path_kernel_w(bool instr) {
+    if (instr) return path_kernel<true, SCENE_LDS, FEAT, WAVES>;
+    return path_kernel<false, SCENE_LDS, FEAT, WAVES>;
 }

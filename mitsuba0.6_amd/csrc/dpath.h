@@ -28,7 +28,7 @@
 #include "layout.h"
 #include "sfmt.h"
 
-#define BLOCK 256
+#define BLOCK MTSG_BLOCK   // layout.h: the host sizes grids, LDS and the wavefront queues by it
 
 // ---------------------------------------------------------------------------
 // Sobol sampler (samplers/sobol.cpp:147-258, sobolseq.h:43-130)
@@ -552,7 +552,7 @@ __device__ __forceinline__ float div_by_rcp(float a, float b, float y) {
 // FAST (axis-aligned groups only): the two quotients through div_by_rcp with
 // the rays' reciprocals yS = RN(1/s_k), yC = RN(1/c_k)
 // The group's first np pairs of records (tris[2i], tris[2i + 1]) share their
-// plane and vertex A bit for bit (capi.cpp mtsg_scan_layout: the two triangles
+// plane and vertex A bit for bit (render_plan.cpp mtsg_scan_layout: the two triangles
 // of a quad), so num, both quotients and each ray's hu, hv are formed once for
 // the two; only the barycentrics and the acceptance run per partner.  Every
 // lane ends with what two successive single iterations give it: partner 1's
@@ -1420,7 +1420,7 @@ struct PathShader {
     // the BSDF-set megakernels are built without strictNormals (the geometric normal
     // is then dead once the hit is formed); scenes with it run the generic kernel
     static constexpr bool NOSTRICT = (FEAT & MTSG_FEAT_NOSTRICT) != 0;
-    // REFN false (MTSG_FEAT_NOREFN, capi.cpp): the scene's only emitter is a non-constant
+    // REFN false (MTSG_FEAT_NOREFN, render_plan.cpp): the scene's only emitter is a non-constant
     // envmap, whose sampleDirect / pdfDirect do not read refN (envmap.cpp:516-556): the area
     // light and constant-emitter code is compiled out and refN (three floats live across the
     // NEE and BSDF calls and the next traversal) is not kept

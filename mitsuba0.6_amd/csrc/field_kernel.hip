@@ -13,6 +13,7 @@
 //
 // Built with path_kernel.hip's flags (Makefile PK_FLAGS): it inlines the same traversal.
 #include "dpath.h"
+#include "launchers.h"
 
 // PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298), as path_kernel.hip's
 __device__ __forceinline__ void field_camera_ray(const MtsgCamera &cam, float sx, float sy, f3 &ro, f3 &rd,
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
     lds_node *ldsNodes = V.nodes;
     lds_tri *ldsTris = V.tris;
     const HitSrc<SCENE_LDS> &hs = V.hs;
-    const SobolCtx &SC = V.SC;   // (no SFMT replay: capi.cpp refuses it)
+    const SobolCtx &SC = V.SC;   // (no SFMT replay: render_plan.cpp refuses it)
     lds_stk_n *stkN = (lds_stk_n *)(lds + V.stackBase) + threadIdx.x;
     lds_stk_d *stkD = (lds_stk_d *)(lds + V.stackBase + L.stack_depth * BLOCK) + threadIdx.x;
     unsigned long long cSamples = 0, cErr = 0, cN = 0, cT = 0;
@@ -159,25 +160,19 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
 // this object's view of the launch record (capi.cpp launch_layout_error)
 extern "C" uint32_t mtsg_launch_bytes_field_kernel() { return (uint32_t)sizeof(MtsgLaunch); }
 
-size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // path_kernel.hip: the same LDS layout
-
-template <int FEAT>
-static hipError_t launch_field_f(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream) {
-    const size_t lds = mtsg_path_lds_bytes(L);
-    if (L.scene_lds) hipLaunchKernelGGL((field_kernel<true, FEAT>), dim3(grid), dim3(BLOCK), lds, stream, L, FA);
-    else hipLaunchKernelGGL((field_kernel<false, FEAT>), dim3(grid), dim3(BLOCK), lds, stream, L, FA);
-    return hipGetLastError();
+// the instantiation of a launch; its dynamic LDS is the megakernel's (mtsg_path_lds_bytes: the same layout)
+typedef void (*FieldKernelFn)(MtsgLaunch, MtsgFieldArgs);
+static FieldKernelFn field_pick(const MtsgLaunch &L) {
+    constexpr int EXT = MTSG_FEAT_EXT, ANA = MTSG_FEAT_EXT | MTSG_FEAT_ANA;
+    if (L.ana) return L.scene_lds ? field_kernel<true, ANA> : field_kernel<false, ANA>;
+    return L.scene_lds ? field_kernel<true, EXT> : field_kernel<false, EXT>;
 }
 
 hipError_t mtsg_launch_field(const MtsgLaunch &L, const MtsgFieldArgs &FA, int grid, hipStream_t stream) {
-    if (L.ana) return launch_field_f<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, FA, grid, stream);
-    return launch_field_f<MTSG_FEAT_EXT>(L, FA, grid, stream);
+    hipLaunchKernelGGL(field_pick(L), dim3(grid), dim3(BLOCK), mtsg_path_lds_bytes(L), stream, L, FA);
+    return hipGetLastError();
 }
 
 int mtsg_field_occupancy(const MtsgLaunch &L, int *bpc) {
-    const size_t lds = mtsg_path_lds_bytes(L);
-#define MTSG_FIELD_OCC(LDS, F) (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(bpc, field_kernel<LDS, F>, BLOCK, lds)
-    if (L.ana) return L.scene_lds ? MTSG_FIELD_OCC(true, MTSG_FEAT_EXT | MTSG_FEAT_ANA) : MTSG_FIELD_OCC(false, MTSG_FEAT_EXT | MTSG_FEAT_ANA);
-    return L.scene_lds ? MTSG_FIELD_OCC(true, MTSG_FEAT_EXT) : MTSG_FIELD_OCC(false, MTSG_FEAT_EXT);
-#undef MTSG_FIELD_OCC
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(bpc, field_pick(L), BLOCK, mtsg_path_lds_bytes(L));
 }

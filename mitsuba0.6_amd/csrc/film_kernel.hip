@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "../../include/mtsgpu.h"
+#include "launchers.h"
 
 namespace {
 

@@ -16,8 +16,7 @@
 #include <vector>
 
 #include "../../include/mtsgpu.h"
-
-hipError_t mtsg_launch_film_accumulate(float *dst, const float *src, size_t n, int num_cus, hipStream_t s);
+#include "launchers.h"
 
 namespace {
 thread_local std::string g_group_create_error;

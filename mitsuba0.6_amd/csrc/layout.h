@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <hip/hip_vector_types.h>   // float4 of MtsgWave (host and device)
 
+#define MTSG_BLOCK 256        // threads per block of every render kernel (dpath.h BLOCK) and of the host's sizing
 #define MTSG_MAX_STACK 64     // BVH builder keeps depth < MTSG_MAX_STACK
 #define MTSG_LEAF_MAX 8       // primitives per leaf
 #define MTSG_SOBOL_DIMS 1024
@@ -110,7 +111,7 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        // BSDF uses GGX / no roughdielectric / no roughconductor in the scene
        MTSG_FEAT_GGX = 16, MTSG_FEAT_NORD = 32, MTSG_FEAT_NORC = 64,
        MTSG_FEAT_INL = 128,     // microfacet / Fresnel helpers inline (the wavefront per-type kernels)
-       MTSG_FEAT_NOSTRICT = 256,     // megakernel BSDF-set variants: strictNormals off (capi.cpp picks the generic kernel otherwise)
+       MTSG_FEAT_NOSTRICT = 256,     // megakernel BSDF-set variants: strictNormals off (render_plan.cpp picks the generic kernel otherwise)
        MTSG_FEAT_NOREFN = 512 };     // BSDF-set variants of scenes lit by a (non-constant) envmap alone: no area
                                      // light and no constant emitter, so DirectSamplingRecord::refN is never read
 enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_DIRECT = 1, MTSG_INTEGRATOR_VOLPATH = 2 };   // = MTSGPU_INTEGRATOR_*
@@ -261,7 +262,7 @@ struct MtsgWave {
     uint2 *ovf;                       // trace stack overflow: [trace lanes][ovf_depth]
     const uint32_t *shape_kind;       // [shapes] MTSG_WK_* of the shape's BSDF
     uint32_t slots;
-    uint32_t cap, cap_cls;            // entries per region of a ray queue / of a kind queue (capi.cpp wf_caps)
+    uint32_t cap, cap_cls;            // entries per region of a ray queue / of a kind queue (render_plan.cpp wf_caps)
     uint32_t parity;                  // bounce index & 1
     uint32_t seed;                    // first bounce: the MISS kernel takes every slot (identity queue)
     uint32_t ovf_depth;
@@ -287,7 +288,7 @@ struct MtsgLaunch {
     uint32_t tiles_x;                 // 8x8 pixel tiles across the window
     uint32_t num_pixels;              // compact pixels incl. padding of partial tiles
     uint32_t j0, chunk_spp;
-    uint32_t round_shift;             // megakernel: a lane renders 2^round_shift samples of a pixel in a row (dmega.h, capi.cpp run_shift)
+    uint32_t round_shift;             // megakernel: a lane renders 2^round_shift samples of a pixel in a row (dmega.h, render_plan.cpp run_shift)
     uint64_t num_items;
     // Sobol direction numbers as 4-bit lookup tables: nib[dim][c][v] = XOR of the
     // columns 4c..4c+3 selected by v (same product as sobolseq.h:43-57)
@@ -301,7 +302,7 @@ struct MtsgLaunch {
     uint32_t ext;                     // kernel variant: roughplastic / textured BSDFs present
     uint32_t ana;                     // kernel variant: analytic shapes present (implies ext)
     uint32_t all_diffuse;             // kernel variant: every BSDF is diffuse (MTSG_FEAT_DIFF)
-    uint32_t bset;                    // the scene's MTSG_FEAT_GGX / NORD / NORC bits (capi.cpp)
+    uint32_t bset;                    // the scene's MTSG_FEAT_GGX / NORD / NORC bits (render_plan.cpp plan_bset)
     uint32_t xcds;                    // XCDs the device's CUs span (workgroup -> XCD remap; 1: none)
     // MTSGPU_FLAG_KDTREE (wavefront engine): wf_trace traverses the reference's kd-tree
     const uint32_t *kd_nodes;         // KDNode words (2 per node), null: the BVH
@@ -313,7 +314,7 @@ struct MtsgLaunch {
                                       // degenerate k = 3 records dropped; counts per group
                                       // in the low 16 bits; the high 16: each group leads with that many pairs
                                       // of records sharing plane and vertex A (partners at 2i, 2i + 1), its
-                                      // singles follow (capi.cpp mtsg_scan_layout)
+                                      // singles follow (render_plan.cpp mtsg_scan_layout)
     uint32_t num_verts, num_shapes;   // sizes of the triangle data SCENE_LDS kernels stage in LDS
     int32_t integrator;               // MTSGPU_INTEGRATOR_*
     uint32_t sampler;                 // MTSGPU_SAMPLER_*
@@ -373,7 +374,7 @@ struct MtsgFieldArgs {
 };
 
 #ifndef MTSG_MIN_RUNS
-#define MTSG_MIN_RUNS 100   // sample runs per lane the megakernel's run length leaves (capi.cpp run_shift)
+#define MTSG_MIN_RUNS 100   // sample runs per lane the megakernel's run length leaves (render_plan.cpp run_shift)
 #endif
 
 #define MTSG_NIBBLES 13

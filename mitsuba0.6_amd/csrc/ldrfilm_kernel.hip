@@ -42,6 +42,7 @@
 
 #include "../../include/mtsgpu.h"
 #include "dmath.h"
+#include "launchers.h"
 
 namespace {
 

@@ -27,91 +27,47 @@ constexpr int spec_feat(int bits) {
 // variants: small scenes (BVH in LDS) run 3 waves/SIMD with 32 Sobol dims in
 // LDS (all-diffuse ones 4: no calls in their bounce loop); large scenes run 4
 // waves/SIMD (128 VGPRs) when the traversal stacks fit 4 blocks per CU, else 3
-// (capi.cpp picks L.waves and L.lds_dims)
+// (render_plan.cpp plan_render picks L.waves and L.lds_dims)
 template <int FEAT>
-void launch_v(const MtsgLaunch &L, int grid, bool instr, hipStream_t stream) {
+PathKernelFn pick_v(const MtsgLaunch &L, bool instr) {
     if constexpr ((FEAT & (MTSG_FEAT_GGX | MTSG_FEAT_NORD | MTSG_FEAT_NORC)) != 0) {   // large scenes only
-        if (L.waves == 4) launch_path_w<false, FEAT, 4>(L, grid, instr, stream);
-        else launch_path_w<false, FEAT, MTSG_WAVES_PER_EU>(L, grid, instr, stream);
+        return L.waves == 4 ? path_kernel_w<false, FEAT, 4>(instr) : path_kernel_w<false, FEAT, MTSG_WAVES_PER_EU>(instr);
     } else {
         if (L.scene_lds) {
             if constexpr ((FEAT & MTSG_FEAT_DIFF) != 0) {
-                if (L.waves == 4) { launch_path_w<true, FEAT, 4>(L, grid, instr, stream); return; }
+                if (L.waves == 4) return path_kernel_w<true, FEAT, 4>(instr);
             }
-            launch_path_w<true, FEAT, MTSG_WAVES_PER_EU>(L, grid, instr, stream);
+            return path_kernel_w<true, FEAT, MTSG_WAVES_PER_EU>(instr);
         }
-        else if (L.waves == 4) launch_path_w<false, FEAT, 4>(L, grid, instr, stream);
-        else launch_path_w<false, FEAT, MTSG_WAVES_PER_EU>(L, grid, instr, stream);
-    }
-}
-template <int FEAT>
-int occupancy_v(const MtsgLaunch &L, int *bpc) {
-    if constexpr ((FEAT & (MTSG_FEAT_GGX | MTSG_FEAT_NORD | MTSG_FEAT_NORC)) != 0) {
-        if (L.waves == 4) return occupancy_w<false, FEAT, 4>(L, bpc);
-        return occupancy_w<false, FEAT, MTSG_WAVES_PER_EU>(L, bpc);
-    } else {
-        if (L.scene_lds) {
-            if constexpr ((FEAT & MTSG_FEAT_DIFF) != 0) {
-                if (L.waves == 4) return occupancy_w<true, FEAT, 4>(L, bpc);
-            }
-            return occupancy_w<true, FEAT, MTSG_WAVES_PER_EU>(L, bpc);
-        }
-        if (L.waves == 4) return occupancy_w<false, FEAT, 4>(L, bpc);
-        return occupancy_w<false, FEAT, MTSG_WAVES_PER_EU>(L, bpc);
+        return L.waves == 4 ? path_kernel_w<false, FEAT, 4>(instr) : path_kernel_w<false, FEAT, MTSG_WAVES_PER_EU>(instr);
     }
 }
 }  // namespace
 
-hipError_t PF_NAME(mtsg_launch_path_f, PATH_FEAT)(const MtsgLaunch &L, int grid, bool instr, hipStream_t s, int bits) {
+// the instantiation mtsg_launch_path launches and mtsg_path_kernel_occupancy sizes the grid by
+// (path_kernel.hip path_pick); bits: spec_bits
+PathKernelFn PF_NAME(mtsg_path_pick_f, PATH_FEAT)(const MtsgLaunch &L, int bits, bool instr) {
     switch (bits) {
-        case 1: launch_v<spec_feat(1)>(L, grid, instr, s); break;
-        case 2: launch_v<spec_feat(2)>(L, grid, instr, s); break;
-        case 3: launch_v<spec_feat(3)>(L, grid, instr, s); break;
-        case 4: launch_v<spec_feat(4)>(L, grid, instr, s); break;
-        case 5: launch_v<spec_feat(5)>(L, grid, instr, s); break;
-        case 6: launch_v<spec_feat(6)>(L, grid, instr, s); break;
-        case 7: launch_v<spec_feat(7)>(L, grid, instr, s); break;
+        case 1: return pick_v<spec_feat(1)>(L, instr);
+        case 2: return pick_v<spec_feat(2)>(L, instr);
+        case 3: return pick_v<spec_feat(3)>(L, instr);
+        case 4: return pick_v<spec_feat(4)>(L, instr);
+        case 5: return pick_v<spec_feat(5)>(L, instr);
+        case 6: return pick_v<spec_feat(6)>(L, instr);
+        case 7: return pick_v<spec_feat(7)>(L, instr);
 #if PATH_FEAT & 1   // envmap-only scenes (MTSG_FEAT_NOREFN): feature sets with an environment emitter
-        case 9: launch_v<spec_feat(9)>(L, grid, instr, s); break;
-        case 10: launch_v<spec_feat(10)>(L, grid, instr, s); break;
-        case 11: launch_v<spec_feat(11)>(L, grid, instr, s); break;
-        case 12: launch_v<spec_feat(12)>(L, grid, instr, s); break;
-        case 13: launch_v<spec_feat(13)>(L, grid, instr, s); break;
-        case 14: launch_v<spec_feat(14)>(L, grid, instr, s); break;
-        case 15: launch_v<spec_feat(15)>(L, grid, instr, s); break;
+        case 9: return pick_v<spec_feat(9)>(L, instr);
+        case 10: return pick_v<spec_feat(10)>(L, instr);
+        case 11: return pick_v<spec_feat(11)>(L, instr);
+        case 12: return pick_v<spec_feat(12)>(L, instr);
+        case 13: return pick_v<spec_feat(13)>(L, instr);
+        case 14: return pick_v<spec_feat(14)>(L, instr);
+        case 15: return pick_v<spec_feat(15)>(L, instr);
 #endif
         default:
 #if PATH_FEAT == 0
-            if (L.all_diffuse) { launch_v<MTSG_FEAT_DIFF>(L, grid, instr, s); break; }
+            if (L.all_diffuse) return pick_v<MTSG_FEAT_DIFF>(L, instr);
 #endif
-            launch_v<PATH_FEAT>(L, grid, instr, s);
-            break;
-    }
-    return hipGetLastError();
-}
-
-int PF_NAME(mtsg_path_occupancy_f, PATH_FEAT)(const MtsgLaunch &L, int bits, int *bpc) {
-    switch (bits) {
-        case 1: return occupancy_v<spec_feat(1)>(L, bpc);
-        case 2: return occupancy_v<spec_feat(2)>(L, bpc);
-        case 3: return occupancy_v<spec_feat(3)>(L, bpc);
-        case 4: return occupancy_v<spec_feat(4)>(L, bpc);
-        case 5: return occupancy_v<spec_feat(5)>(L, bpc);
-        case 6: return occupancy_v<spec_feat(6)>(L, bpc);
-        case 7: return occupancy_v<spec_feat(7)>(L, bpc);
-#if PATH_FEAT & 1
-        case 9: return occupancy_v<spec_feat(9)>(L, bpc);
-        case 10: return occupancy_v<spec_feat(10)>(L, bpc);
-        case 11: return occupancy_v<spec_feat(11)>(L, bpc);
-        case 12: return occupancy_v<spec_feat(12)>(L, bpc);
-        case 13: return occupancy_v<spec_feat(13)>(L, bpc);
-        case 14: return occupancy_v<spec_feat(14)>(L, bpc);
-        case 15: return occupancy_v<spec_feat(15)>(L, bpc);
-#endif
-        default:
-#if PATH_FEAT == 0
-            if (L.all_diffuse) return occupancy_v<MTSG_FEAT_DIFF>(L, bpc);
-#endif
-            return occupancy_v<PATH_FEAT>(L, bpc);
+            return pick_v<PATH_FEAT>(L, instr);
     }
 }

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
     lds_node *ldsNodes = V.nodes;
     lds_tri *ldsTris = V.tris;
     const HitSrc<SCENE_LDS> &hs = V.hs;
-    // (the SFMT replay renders path / volpath only, capi.cpp: V.SC.replay is false here)
+    // (the SFMT replay renders path / volpath only, render_plan.cpp: V.SC.replay is false here)
     const SobolCtx &SC = V.SC;
     lds_stk_n *stkN = (lds_stk_n *)(lds + V.stackBase) + threadIdx.x;
     lds_stk_d *stkD = (lds_stk_d *)(lds + V.stackBase + L.stack_depth * BLOCK) + threadIdx.x;
@@ -677,7 +677,7 @@ __global__ void arith_probe(const float *a, const float *b, float *out, int n) {
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called by capi.cpp)
+// host-side launchers (launchers.h)
 // ---------------------------------------------------------------------------
 // this object's view of the launch record (capi.cpp launch_layout_error)
 extern "C" uint32_t mtsg_launch_bytes_path_kernel() { return (uint32_t)sizeof(MtsgLaunch); }
@@ -692,13 +692,7 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
     return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS + scene + tail) * 4;
 }
 
-// the megakernel variants, one object per scene feature set (path_f.hip)
-#define MTSG_PATH_F_DECL(N)                                                                                  \
-    hipError_t mtsg_launch_path_f##N(const MtsgLaunch &L, int grid, bool instr, hipStream_t s, int bits);   \
-    int mtsg_path_occupancy_f##N(const MtsgLaunch &L, int bits, int *bpc);
-MTSG_PATH_F_DECL(0) MTSG_PATH_F_DECL(1) MTSG_PATH_F_DECL(2) MTSG_PATH_F_DECL(3) MTSG_PATH_F_DECL(6)
-MTSG_PATH_F_DECL(7)
-#undef MTSG_PATH_F_DECL
+bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L); }
 
 int mtsg_path_features(const MtsgLaunch &L) {
     return (L.scene.env_emitter >= 0 ? MTSG_FEAT_ENV : 0) | ((L.ext || L.ana) ? MTSG_FEAT_EXT : 0) |
@@ -707,12 +701,26 @@ int mtsg_path_features(const MtsgLaunch &L) {
 
 // The BSDF-set specialisation (dbsdf.h BSet) of large scenes: bit 0 = every
 // rough BSDF uses GGX, bit 1 = no roughdielectric, bit 2 = no roughconductor
-// (capi.cpp L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
+// (render_plan.cpp plan_render, L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
 // small scenes staged in LDS and the direct integrator take the generic kernel.
 static int spec_bits(const MtsgLaunch &L) {
     if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT) return 0;
     const int b = ((L.bset & MTSG_FEAT_GGX) ? 1 : 0) | ((L.bset & MTSG_FEAT_NORD) ? 2 : 0) | ((L.bset & MTSG_FEAT_NORC) ? 4 : 0);
     return b | ((b && (L.bset & MTSG_FEAT_NOREFN) && (mtsg_path_features(L) & MTSG_FEAT_ENV)) ? 8 : 0);
+}
+
+// the megakernel instantiation of a launch, one object per scene feature set (path_f.hip):
+// mtsg_launch_path launches it, mtsg_path_kernel_occupancy sizes the grid by it
+static PathKernelFn path_pick(const MtsgLaunch &L, bool instr) {
+    const int bits = spec_bits(L);
+    switch (mtsg_path_features(L)) {
+        case 0: return mtsg_path_pick_f0(L, bits, instr);
+        case MTSG_FEAT_ENV: return mtsg_path_pick_f1(L, bits, instr);
+        case MTSG_FEAT_EXT: return mtsg_path_pick_f2(L, bits, instr);
+        case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_path_pick_f3(L, bits, instr);
+        case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_pick_f6(L, bits, instr);
+        default: return mtsg_path_pick_f7(L, bits, instr);
+    }
 }
 
 template <int FEAT>
@@ -735,15 +743,8 @@ hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool st
         }
         return hipGetLastError();
     }
-    const int bits = spec_bits(L);
-    switch (mtsg_path_features(L)) {
-        case 0: return mtsg_launch_path_f0(L, grid, instr, stream, bits);
-        case MTSG_FEAT_ENV: return mtsg_launch_path_f1(L, grid, instr, stream, bits);
-        case MTSG_FEAT_EXT: return mtsg_launch_path_f2(L, grid, instr, stream, bits);
-        case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_launch_path_f3(L, grid, instr, stream, bits);
-        case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_launch_path_f6(L, grid, instr, stream, bits);
-        default: return mtsg_launch_path_f7(L, grid, instr, stream, bits);
-    }
+    hipLaunchKernelGGL(path_pick(L, instr), dim3(grid), dim3(BLOCK), mtsg_path_lds_bytes(L), stream, L);
+    return hipGetLastError();
 }
 
 hipError_t mtsg_launch_reduce(const MtsgLaunch &L, hipStream_t stream) {
@@ -826,13 +827,6 @@ int mtsg_path_variant(const MtsgLaunch &L) {
 }
 
 int mtsg_path_kernel_occupancy(const MtsgLaunch &L, int *blocksPerCU) {
-    const int bits = spec_bits(L);
-    switch (mtsg_path_features(L)) {
-        case 0: return mtsg_path_occupancy_f0(L, bits, blocksPerCU);
-        case MTSG_FEAT_ENV: return mtsg_path_occupancy_f1(L, bits, blocksPerCU);
-        case MTSG_FEAT_EXT: return mtsg_path_occupancy_f2(L, bits, blocksPerCU);
-        case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_path_occupancy_f3(L, bits, blocksPerCU);
-        case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_occupancy_f6(L, bits, blocksPerCU);
-        default: return mtsg_path_occupancy_f7(L, bits, blocksPerCU);
-    }
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, path_pick(L, false), BLOCK,
+                                                             mtsg_path_lds_bytes(L));
 }

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "dmath.h"
+#include "launchers.h"
 
 namespace {
 

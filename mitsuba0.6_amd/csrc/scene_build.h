@@ -51,6 +51,11 @@ struct HostScene {
     std::vector<float> rtrans, texcoords;
     bool ext = false;   // roughplastic or textured BSDFs: the MTSG_FEAT_EXT kernel variant
     std::vector<MtsgAnalytic> analytic;   // rectangle / disk / sphere records (MTSG_FEAT_ANA variant)
+    // launch constants of the scene, formed where it is uploaded (render_plan.cpp scene_scan_n, scene_one_emitter)
+    struct {
+        uint32_t scan_n[6];     // as MtsgLaunch::scan_n: records | plane pairs << 16
+        uint32_t one_emitter;   // the emitter CDF is {0.0f, 1.0f} bit for bit (MtsgLaunch::one_emitter)
+    } launch = {};
 };
 
 // Returns MTSGPU_OK or an error code; `err` receives the message.

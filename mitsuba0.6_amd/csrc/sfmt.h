@@ -64,4 +64,4 @@ SFMT_FN float sfmt_next_float(P w) {
     return f - 1.0f;
 }
 
-// host-side seeding (Random(seed), Random(&parent)): capi.cpp mtsg_sfmt_seed / mtsg_sfmt_clone
+// host-side seeding (Random(seed), Random(&parent)): replay_host.cpp mtsg_sfmt_seed / mtsg_sfmt_clone

@@ -2,10 +2,10 @@
 // launchers (the engine: wf_impl.h; its shade kernels are compiled per scene
 // feature set in wf_shade_f.hip, one object per set, so they build in parallel)
 #include "wf_impl.h"
+#include "launchers.h"
 
 #include <cstdlib>
 
-int mtsg_path_features(const MtsgLaunch &L);   // path_kernel.hip
 #define MTSG_WF_PICK_DECL(N) WfShadeFn mtsg_wf_pick_##N(int wk, bool instr, bool ggx);
 MTSG_WF_PICK_DECL(0) MTSG_WF_PICK_DECL(1) MTSG_WF_PICK_DECL(2) MTSG_WF_PICK_DECL(3) MTSG_WF_PICK_DECL(6)
 MTSG_WF_PICK_DECL(7)
@@ -20,7 +20,7 @@ __global__ void wf_flush(const unsigned long long *part, uint32_t blocks, unsign
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (capi.cpp)
+// host-side launchers (launchers.h)
 // ---------------------------------------------------------------------------
 // this object's view of the launch record (capi.cpp launch_layout_error)
 extern "C" uint32_t mtsg_launch_bytes_wf_kernel() { return (uint32_t)sizeof(MtsgLaunch); }

@@ -2,6 +2,7 @@
 // scene feature set WF_FEAT (MTSG_FEAT_ENV | EXT | ANA bits), built once per
 // set by the Makefile (-DWF_FEAT=n -> wf_shade_f<n>.o)
 #include "wf_impl.h"
+#include "launchers.h"
 
 #define MTSG_WF_PICK_NAME2(N) mtsg_wf_pick_##N
 #define MTSG_WF_PICK_NAME(N) MTSG_WF_PICK_NAME2(N)

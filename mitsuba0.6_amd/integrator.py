@@ -35,7 +35,7 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
            'mtsgpu_face_normals_host', 'mtsgpu_render_fields', 'mtsgpu_render_fields_device', 'mtsgpu_develop_multi',
            'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_develop_ldr',
-           'mtsgpu_develop_ldr_device']
+           'mtsgpu_develop_ldr_device', 'mtsgpu_plan_host']
 
 _lib = None
 
@@ -109,6 +109,9 @@ def load_library(path=None):
         L.mtsgpu_develop_ldr.argtypes = [C.c_void_p, P(abi.DevelopLdrParams), P(C.c_float), C.c_void_p, P(C.c_float)]
         L.mtsgpu_develop_ldr_device.argtypes = [C.c_void_p, P(abi.DevelopLdrParams), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, P(C.c_float)]
+    if hasattr(L, 'mtsgpu_plan_host'):   # added within ABI 8 as well (the render plan without a device)
+        L.mtsgpu_plan_host.argtypes = [P(abi.SceneDesc), P(abi.RenderParams), C.c_uint32, C.c_int, P(C.c_uint64),
+                                       P(C.c_uint64), C.c_size_t, C.c_char_p, C.c_size_t]
     L.mtsgpu_group_create.argtypes = [P(C.c_int), C.c_int, P(C.c_void_p)]
     L.mtsgpu_group_size.argtypes = [C.c_void_p]
     L.mtsgpu_group_upload_scene.argtypes = [C.c_void_p, P(abi.SceneDesc)]
@@ -242,6 +245,62 @@ def lookup_host(m, scramble, px_py_j):
     return out
 
 
+PLAN_ENGINES = ('megakernel', 'wavefront', 'fields')
+
+
+def kernel_variant_of(word):
+    """Debug counter 15 (render_plan.cpp plan_variant_word) decoded: {'instr', 'scene_lds',
+    'feat', 'waves', 'name'}, name being the megakernel's template as rocprofv3 reports it,
+    e.g. 'path_kernel<false, false, 336, 4>'; None for the wavefront engine and a field pass."""
+    c = int(word)
+    if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
+        return None
+    feat = (c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0)
+    instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
+    b = lambda v: 'true' if v else 'false'
+    return {'instr': instr, 'scene_lds': lds, 'feat': feat, 'waves': waves,
+            'name': 'path_kernel<%s, %s, %d, %d>' % (b(instr), b(lds), feat, waves)}
+
+
+def plan_host(scene, integ, fields=None, window=None, samples=False, row=(0, 1, 0), tile_shard=False, engine=None,
+              cus=256, blocks_per_cu=0, free_bytes=0, params=None, max_launches=64):
+    """What a render of `scene` with `integ` would launch, planned on the host without a
+    device (mtsgpu_plan_host) by the functions the renders run, under the MTSGPU_*
+    environment of the call.  The arguments are Context.render's (fields: a list of
+    FieldIntegrators or names, as Context.render_fields); cus, blocks_per_cu (0: the plan's
+    waves per SIMD) and free_bytes (0: unknown) describe the device; params: a ready
+    abi.RenderParams instead of integ's.  Returns a dict: 'engine', 'variant_word' (what debug
+    counter 15 would read), 'variant' (kernel_variant_of it), 'pixels' (compact), 'chunk',
+    'launches', 'waves', 'lds_dims', 'nibbles', 'scene_lds', 'scan', 'start_queue', 'gather',
+    'replay', 'gather_h', 'lds_bytes', 'wf_slots' and 'launch': the first max_launches
+    launches as (chunk_spp, grid, round_shift).  Raises MtsgpuError as the render would."""
+    L = load_library()
+    d = scene.desc()
+    if params is None:
+        W, H = scene.sensor.width, scene.sensor.height
+        x0, y0, w, h = window if window else (integ.crop or (0, 0, W, H))
+        params = integ.params(W, H, x0, y0, w, h, row[0], row[1], row[2])
+        if tile_shard:
+            params.flags |= abi.FLAG_TILE_SHARD
+        params.flags |= Context._engine_flags(engine)
+    cap = 16 + 3 * max_launches
+    out = (C.c_uint64 * cap)()
+    dev = (C.c_uint64 * 3)(cus, blocks_per_cu, free_bytes)
+    buf = C.create_string_buffer(1024)
+    rc = L.mtsgpu_plan_host(C.byref(d), C.byref(params), len(fields) if fields else 0, 1 if samples else 0, dev, out,
+                            cap, buf, 1024)
+    if rc != 0:
+        raise MtsgpuError(rc, buf.value.decode())
+    n = min(int(out[4]), max_launches)
+    bits = int(out[8])
+    return {'engine': PLAN_ENGINES[out[0]], 'variant_word': int(out[1]), 'variant': kernel_variant_of(out[1]),
+            'pixels': int(out[2]), 'chunk': int(out[3]), 'launches': int(out[4]), 'waves': int(out[5]),
+            'lds_dims': int(out[6]), 'nibbles': int(out[7]), 'scene_lds': bool(bits & 1), 'scan': bool(bits & 2),
+            'start_queue': bool(bits & 4), 'gather': bool(bits & 8), 'replay': bool(bits & 16),
+            'gather_h': int(out[9]), 'lds_bytes': int(out[10]), 'wf_slots': int(out[11]),
+            'launch': [(int(out[16 + 3 * i]), int(out[17 + 3 * i]), int(out[18 + 3 * i])) for i in range(n)]}
+
+
 def kdtree_host(scene):
     """The reference's SAH kd-tree of `scene`, built on the host without a device
     (mtsgpu_kdtree_host): (nodes (N, 2) uint32 KDNode words, indices, info dict)."""
@@ -295,17 +354,8 @@ class Context:
 
     def kernel_variant(self):
         """The megakernel instantiation the last render launched, decoded from debug
-        counter 15 (capi.cpp): {'instr', 'scene_lds', 'feat', 'waves', 'name'}, where
-        name is the template as rocprofv3 reports it, e.g.
-        'path_kernel<false, false, 336, 4>'; None after a wavefront-engine render."""
-        c = self.debug_counters()[15]
-        if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
-            return None
-        feat = (c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0)
-        instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
-        b = lambda v: 'true' if v else 'false'
-        return {'instr': instr, 'scene_lds': lds, 'feat': feat, 'waves': waves,
-                'name': 'path_kernel<%s, %s, %d, %d>' % (b(instr), b(lds), feat, waves)}
+        counter 15 (kernel_variant_of); None after a wavefront-engine render or a field pass."""
+        return kernel_variant_of(self.debug_counters()[15])
 
     def debug_sfmt(self, seed, n, clone=0):
         """n nextULong draws of the device's SFMT19937 from Random(seed) (or its clone-th clone)."""

@@ -1,5 +1,5 @@
 """Megakernel sample runs (dmega.h): a lane renders 2^s consecutive samples of one
-pixel (s = MtsgLaunch::round_shift, chosen per chunk by capi.cpp run_shift, or
+pixel (s = MtsgLaunch::round_shift, chosen per chunk by render_plan.cpp run_shift, or
 forced with MTSGPU_ROUND_SHIFT).  The work decomposition must not change a
 single bit: every (pixel, sample) is rendered exactly once, whatever s, the
 chunk's spp (13: not a multiple of 2^s; 3: fewer samples than a run) and the

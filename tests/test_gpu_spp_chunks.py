@@ -1,6 +1,6 @@
-"""Renders whose sample count is split into several launches (capi.cpp render_impl).
+"""Renders whose sample count is split into several launches (csrc/render_plan.cpp, capi.cpp render_impl).
 
-render_impl sizes the per-sample record buffer against a budget and, when the
+plan_render sizes the per-sample record buffer against a budget and, when the
 frame's samples do not fit, loops over chunks of the sample count: L.j0,
 L.chunk_spp and L.num_items change per launch, the run shift is chosen per chunk,
 and film_reduce / film_gather continue the running float32 sums of the launches
@@ -43,8 +43,8 @@ def _ceil_div(a, b):
 
 
 def chunk_plan(size, spp, gaussian, n_films=1, row=(0, 1, 0), tile_shard=False):
-    """(chunk, launches, compact pixels) of a render of a size = (w, h) window: capi.cpp's
-    launch_geometry and the budget arithmetic of render_impl, restated."""
+    """(chunk, launches, compact pixels) of a render of a size = (w, h) window: render_plan.cpp's
+    launch_geometry and the budget arithmetic of plan_render, restated."""
     w, h = size
     block, stride = row[0] or 1, row[1] or 1
     tiles_x = _ceil_div(w, 8)

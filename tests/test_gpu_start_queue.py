@@ -37,7 +37,7 @@ def _ceil_div(a, b):
 
 
 def compact_pixels(size, row=(0, 1, 0), tile_shard=False):
-    """Compact pixels (padding included) of a size = (w, h) window: capi.cpp launch_geometry."""
+    """Compact pixels (padding included) of a size = (w, h) window: render_plan.cpp launch_geometry."""
     w, h = size
     block, stride = row[0] or 1, row[1] or 1
     tiles_x = _ceil_div(w, 8)
@@ -49,7 +49,7 @@ def compact_pixels(size, row=(0, 1, 0), tile_shard=False):
 def queue_plan(num_pixels, spp, cus, shift=None, chunk=None):
     """Production passes of a render: per launch, over the waves of its grid, the
     steps of the wave's first lane plus the pass that finds every lane exhausted
-    (capi.cpp render_impl and run_shift, layout.h mtsg_run_step, restated)."""
+    (render_plan.cpp plan_launch and run_shift, layout.h mtsg_run_step, restated)."""
     chunk = chunk or spp
     total = 0
     for j0 in range(0, spp, chunk):

@@ -22,7 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 # ---- the item -> pixel rule restated with Python integers -------------------------------
 def geometry(window, row, tile_shard):
-    """(compact pixels, tiles across) of a launch (capi.cpp render_impl)."""
+    """(compact pixels, tiles across) of a launch (render_plan.cpp launch_geometry)."""
     _, _, w, h = window
     rb, rs_, _ = max(row[0], 1), max(row[1], 1), row[2]
     tiles_x = (w + 7) // 8
