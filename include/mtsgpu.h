@@ -109,7 +109,13 @@ typedef struct {
 
 enum { MTSGPU_EMITTER_AREA = 0,      /* area.cpp: on a shape (mesh_desc.emitter)          */
        MTSGPU_EMITTER_ENVMAP = 1,    /* envmap.cpp: lat-long image (env_* fields)          */
-       MTSGPU_EMITTER_CONSTANT = 2   /* constant.cpp: uniform 'radiance' environment       */
+       MTSGPU_EMITTER_CONSTANT = 2,  /* constant.cpp: uniform 'radiance' environment       */
+       /* delta emitters: `radiance` carries 'intensity' (point, spot) or 'irradiance'
+          (directional); env_to_world / env_to_world_inv carry the emitter's 'toWorld' and
+          the inverse its Transform carries (all zero: the library inverts)               */
+       MTSGPU_EMITTER_POINT = 3,     /* point.cpp                                          */
+       MTSGPU_EMITTER_SPOT = 4,      /* spot.cpp: cutoff_angle, beam_width (constant texture) */
+       MTSGPU_EMITTER_DIRECTIONAL = 5 /* directional.cpp: toWorld without scale            */
 };
 
 typedef struct {
@@ -124,6 +130,11 @@ typedef struct {
     float env_to_world_inv[16];     /* its inverse as the reference's Transform    */
                                     /* carries it (transform.cpp); all zero: the   */
                                     /* library inverts env_to_world (Gauss-Jordan) */
+    /* spot.cpp, in degrees.  Appended after ABI version 8 was cut: no earlier     */
+    /* offset moved and the version number stays; a caller that describes a spot   */
+    /* emitter must pass the struct with these two fields                          */
+    float cutoff_angle;             /* 'cutoffAngle' (20)                          */
+    float beam_width;               /* 'beamWidth' (3/4 cutoffAngle)               */
 } mtsgpu_emitter_desc;
 
 enum { /* shape plugins (src/shapes) */
@@ -596,7 +607,9 @@ int mtsgpu_debug_libm(mtsgpu_ctx *ctx, int fn, const float *a, const float *b, f
    kernel that ran: the megakernel's feature set (MTSG_FEAT_* bits of
    csrc/layout.h, BSDF-set bits included) | waves/SIMD << 8 | scene in LDS << 12,
    1 << 16 for the wavefront engine, or 1 << 17 | scene in LDS << 12 after a
-   field pass (mtsgpu_render_fields) */
+   field pass (mtsgpu_render_fields); 1 << 18 on top of the megakernel's, the
+   direct kernel's or the wavefront engine's word when the instantiations of a
+   scene with delta emitters (point, spot, directional) ran */
 int mtsgpu_debug_counters(mtsgpu_ctx *ctx, uint64_t *out16);
 /* n nextULong draws of the device's SFMT19937 (the SFMT replay samplers' generator)
    from Random(seed), or from the clone-th Random(&master) clone of it */

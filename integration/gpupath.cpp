@@ -214,6 +214,28 @@ public:
             } else if (cls == "AreaLight") {                          /* area.cpp */
                 d.type = MTSGPU_EMITTER_AREA;
                 toRGB(p.getSpectrum("radiance", Spectrum::getD65()), d.radiance);
+            } else if (cls == "PointEmitter" || cls == "SpotEmitter" || cls == "DirectionalEmitter") {
+                /* the delta emitters: the transform the constructor built (from 'position' /
+                   'direction' or 'toWorld') and its carried inverse, point.cpp:57-69,
+                   spot.cpp:68-78, directional.cpp:55-73 */
+                const Transform &t = e->getWorldTransform()->eval(0);
+                copyMatrix(t.getMatrix(), d.env_to_world);
+                copyMatrix(t.getInverseMatrix(), d.env_to_world_inv);
+                if (cls == "PointEmitter") {
+                    d.type = MTSGPU_EMITTER_POINT;
+                    toRGB(p.getSpectrum("intensity", Spectrum::getD65()), d.radiance);
+                } else if (cls == "SpotEmitter") {
+                    /* (a texture given as a child object stays private to the plugin, spot.cpp:76-78) */
+                    if (p.hasProperty("texture"))
+                        Log(EError, "spot emitter: a projection texture is not supported");
+                    d.type = MTSGPU_EMITTER_SPOT;
+                    toRGB(p.getSpectrum("intensity", Spectrum(1.0f)), d.radiance);
+                    d.cutoff_angle = (float) p.getFloat("cutoffAngle", 20);
+                    d.beam_width = (float) p.getFloat("beamWidth", d.cutoff_angle * 3.0f / 4.0f);
+                } else {
+                    d.type = MTSGPU_EMITTER_DIRECTIONAL;
+                    toRGB(p.getSpectrum("irradiance", Spectrum::getD65()), d.radiance);
+                }
             } else {
                 Log(EError, "emitter \"%s\" is not supported", cls.c_str());
             }

@@ -18,6 +18,7 @@ ABI_VERSION = 8
 TRACE_SHADOW, TRACE_KDTREE = 1, 2           # mtsgpu_trace_rays_ex flags
 DISTR_BECKMANN, DISTR_GGX, DISTR_PHONG = 0, 1, 2
 EMITTER_AREA, EMITTER_ENVMAP, EMITTER_CONSTANT = 0, 1, 2
+EMITTER_POINT, EMITTER_SPOT, EMITTER_DIRECTIONAL = 3, 4, 5
 SHAPE_TRIMESH, SHAPE_RECTANGLE, SHAPE_DISK, SHAPE_SPHERE = 0, 1, 2, 3
 FOV_X, FOV_Y, FOV_DIAGONAL, FOV_SMALLER, FOV_LARGER = 0, 1, 2, 3, 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
@@ -57,7 +58,8 @@ class BsdfDesc(C.Structure):
 class EmitterDesc(C.Structure):
     _fields_ = [('type', C.c_int32), ('radiance', _f3), ('sampling_weight', C.c_float),
                 ('env_rgb', C.POINTER(C.c_float)), ('env_width', C.c_uint32), ('env_height', C.c_uint32),
-                ('env_scale', C.c_float), ('env_to_world', _f16), ('env_to_world_inv', _f16)]
+                ('env_scale', C.c_float), ('env_to_world', _f16), ('env_to_world_inv', _f16),
+                ('cutoff_angle', C.c_float), ('beam_width', C.c_float)]
 
 
 class MeshDesc(C.Structure):

@@ -60,7 +60,7 @@ struct mtsgpu_ctx {
     DevBuf face_n;   // unit face normals per primitive (MtsgLaunch::face_n)
     DevBuf nodes, hnodes, tris, prim_vtx, dpdu, positions, normals, shapes, bsdfs, emitters, area_cdf, em_cdf, sobol;
     DevBuf env, env_texels, env_rows, env_cols, env_weights, env_grows, env_gcols;
-    DevBuf rtrans, texcoords, analytic;
+    DevBuf rtrans, texcoords, analytic, delta;
     DevBuf qrays, qhits;      // mtsgpu_trace_rays staging
     DevBuf film_own, film_spill, samples, counters, contrib;
     DevBuf dev_in, dev_out;   // staging of mtsgpu_develop (host film -> developed image)
@@ -95,6 +95,7 @@ const std::string &launch_layout_error() {
             {"field_kernel", mtsg_launch_bytes_field_kernel()},
 #define MTSG_BYTES_ROW(N) {"path_f" #N, mtsg_launch_bytes_path_f##N()}, {"wf_shade_f" #N, mtsg_launch_bytes_wf_shade_f##N()},
             MTSG_BYTES_ROW(0) MTSG_BYTES_ROW(1) MTSG_BYTES_ROW(2) MTSG_BYTES_ROW(3) MTSG_BYTES_ROW(6) MTSG_BYTES_ROW(7)
+            MTSG_BYTES_ROW(1031)
 #undef MTSG_BYTES_ROW
         };
         for (const auto &o : objs)
@@ -243,7 +244,8 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     }
     if ((!H.rtrans.empty() && (e = upload(ctx->rtrans, H.rtrans, s)) != hipSuccess) ||
         (!H.texcoords.empty() && (e = upload(ctx->texcoords, H.texcoords, s)) != hipSuccess) ||
-        (!H.analytic.empty() && (e = upload(ctx->analytic, H.analytic, s)) != hipSuccess))
+        (!H.analytic.empty() && (e = upload(ctx->analytic, H.analytic, s)) != hipSuccess) ||
+        (!H.deltas.empty() && (e = upload(ctx->delta, H.deltas, s)) != hipSuccess))
         return hip_fail(ctx, e, "texture/table upload");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "scene upload sync");
     MtsgDeviceScene &D = ctx->dscene;
@@ -266,6 +268,7 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     D.rtrans = H.rtrans.empty() ? nullptr : (const float *)ctx->rtrans.p;
     D.texcoords = H.texcoords.empty() ? nullptr : (const float *)ctx->texcoords.p;
     D.analytic = H.analytic.empty() ? nullptr : (const MtsgAnalytic *)ctx->analytic.p;
+    D.delta = H.deltas.empty() ? nullptr : (const MtsgDelta *)ctx->delta.p;
     ctx->have_scene = true;
     return MTSGPU_OK;
 }
@@ -879,7 +882,7 @@ void mtsgpu_destroy(mtsgpu_ctx *ctx) {
                       &ctx->shapes, &ctx->bsdfs, &ctx->emitters, &ctx->area_cdf, &ctx->em_cdf, &ctx->sobol,
                       &ctx->film_own, &ctx->film_spill, &ctx->samples, &ctx->counters, &ctx->contrib,
                       &ctx->env, &ctx->env_texels, &ctx->env_rows, &ctx->env_cols, &ctx->env_weights, &ctx->env_grows, &ctx->env_gcols,
-                      &ctx->rtrans, &ctx->texcoords, &ctx->qrays, &ctx->qhits, &ctx->field_first,
+                      &ctx->rtrans, &ctx->texcoords, &ctx->delta, &ctx->qrays, &ctx->qhits, &ctx->field_first,
                       &ctx->dev_in, &ctx->dev_out, &ctx->ldr_scratch, &ctx->wf_state, &ctx->wf_ray, &ctx->wf_rslot, &ctx->wf_cls,
                       &ctx->wf_cnt, &ctx->wf_hit, &ctx->wf_hitrec, &ctx->wf_occl, &ctx->wf_live, &ctx->wf_ovf, &ctx->wf_part, &ctx->wf_kind, &ctx->rp_order, &ctx->rp_start, &ctx->rp_sfmt, &ctx->env_grows, &ctx->env_gcols};
     for (DevBuf *b : bufs) b->release();

@@ -24,6 +24,7 @@
 
 #include "danalytic.h"
 #include "dbsdf.h"
+#include "ddelta.h"
 #include "denv.h"
 #include "layout.h"
 #include "sfmt.h"
@@ -1425,6 +1426,14 @@ struct PathShader {
     // light and constant-emitter code is compiled out and refN (three floats live across the
     // NEE and BSDF calls and the next traversal) is not kept
     static constexpr bool REFN = (FEAT & MTSG_FEAT_NOREFN) == 0;
+    // DELTA (MTSG_FEAT_DELTA): the scene has point / spot / directional emitters (ddelta.h).  Its one
+    // feature set is compiled with ENV, which such a scene need not have: have_env() asks the scene
+    // there and is the constant `true` in every other kernel
+    static constexpr bool DELTA = (FEAT & MTSG_FEAT_DELTA) != 0;
+    __device__ __forceinline__ bool have_env() const {
+        if constexpr (DELTA) return L.scene.env_emitter >= 0;
+        else return true;
+    }
     const MtsgLaunch &L;
     const HitSrc<SCENE_LDS> &hs;
     const SobolCtx &SC;
@@ -1569,7 +1578,7 @@ struct PathShader {
                 vertex = true;
             } else if (HITK == 2 || !P.its.valid) {
                 // missed: the environment emitter, if any (path.cpp:233-247)
-                if (ENV && !(L.hide_emitters && !P.scattered)) {
+                if (ENV && have_env() && !(L.hide_emitters && !P.scattered)) {
                     glb_env *E = (glb_env *)S.env;
                     const bool cst = REFN && E->constant;
                     EnvValPdf vp = {mk(0, 0, 0), 0.0f};
@@ -1632,7 +1641,7 @@ struct PathShader {
             } else if (HITK == 2 || !P.its.valid) {
                 // camera ray missed: scene->evalEnvironment(ray) with the sensor's ray
                 // differentials (path.cpp:136-142, perspective.cpp:271-298, integrator.cpp:181)
-                if (ENV && P.emitted && (!L.hide_emitters || P.scattered)) {
+                if (ENV && have_env() && P.emitted && (!L.hide_emitters || P.scattered)) {
                     const MtsgCamera &cam = S.cam;
                     const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
                     const f3 rxl = normalize(add(nearP, ld3(cam.dx))), ryl = normalize(add(nearP, ld3(cam.dy)));
@@ -1696,7 +1705,18 @@ struct PathShader {
                         float pdf = 0.0f, dist = 0.0f;
                         f3 vlp = mk(0, 0, 0);   // dRec.p where it does not define dRec.d exactly (volpath)
                         bool vrecomp = false;
-                        if (ENV && (!REFN || e.type != MTSG_EMITTER_AREA)) {
+                        bool onSurface = true;   // Emitter::isOnSurface(): false for the delta emitters
+                        bool isDelta = false;
+                        if constexpr (DELTA) isDelta = e.type >= MTSG_EMITTER_POINT;
+                        if (DELTA && isDelta) {
+                            if constexpr (DELTA) {
+                                const DeltaSample ds =
+                                    delta_sample_direct(e.type, ((GDelta *)S.delta)[e.tri_first], ld3(e.radiance), P.its.p);
+                                value = ds.value; dd = ds.d; dist = ds.dist; pdf = ds.pdf;
+                                vlp = ds.p; vrecomp = true;
+                                onSurface = false;
+                            }
+                        } else if (ENV && (!REFN || e.type != MTSG_EMITTER_AREA)) {
                             glb_env *E = (glb_env *)S.env;
                             const EnvSample es = (REFN && E->constant) ? const_sample_direct(E, P.its.p, P.refN, ex, ey)
                                                                        : env_sample_direct(E, P.its.p, ex, ey);
@@ -1774,7 +1794,8 @@ struct PathShader {
                                                                               P.its.u, P.its.v, rpPre(qb, qwi));
                                 const f3 bsdfVal = ep.val;
                                 if (!is_zero(bsdfVal) && (NOSTRICT || !L.strict_normals || dot(P.its.geoN, dd) * wo.z > 0)) {
-                                    const float bsdfPdf = ep.pdf;
+                                    // bsdfPdf = 0 for an emitter that is not on a surface (path.cpp:192-197)
+                                    const float bsdfPdf = (DELTA && !onSurface) ? 0.0f : ep.pdf;
                                     const float pa = dpdf * dpdf, pb = bsdfPdf * bsdfPdf;
                                     const float weight = pa / (pa + pb);
                                     c = mul(mulv(mulv(P.thr, value), bsdfVal), weight);
@@ -1786,12 +1807,13 @@ struct PathShader {
                             smaxt = dist * (1 - D_SHADOW_EPSILON);
                             if (L.integrator == MTSG_INTEGRATOR_VOLPATH && vrecomp) {
                                 // Scene::evalTransmittance (scene.cpp:619-679, 890): the segment to dRec.p,
-                                // re-normalised; every supported emitter is EOnSurface (envmap.cpp:107,
-                                // constant.cpp:48, area lights), so the shadow epsilon always applies
+                                // re-normalised; area lights and the environment are EOnSurface (envmap.cpp:107,
+                                // constant.cpp:48) and get the shadow epsilon at the far end, the delta
+                                // emitters (p2OnSurface = false) the whole segment: lengthFactor = 1
                                 const f3 v = sub(vlp, P.its.p);
                                 const float rem = dsqrt(len2(v));
                                 sd = divs(v, rem);
-                                smaxt = rem * (1 - D_SHADOW_EPSILON);
+                                smaxt = (DELTA && !onSurface) ? rem * 1.0f : rem * (1 - D_SHADOW_EPSILON);
                             }
                             st.haveShadow = true;
                         }

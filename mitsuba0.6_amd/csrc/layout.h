@@ -104,7 +104,9 @@ struct MtsgBsdf {            // configured BSDF (after ctor + configure)
     int32_t nested[2];
 };
 
-enum { MTSG_EMITTER_AREA = 0, MTSG_EMITTER_ENVMAP = 1, MTSG_EMITTER_CONSTANT = 2 };
+enum { MTSG_EMITTER_AREA = 0, MTSG_EMITTER_ENVMAP = 1, MTSG_EMITTER_CONSTANT = 2,
+       // delta emitters (ddelta.h): one NEE candidate with pdf 1, EDiscrete, never hit by a ray
+       MTSG_EMITTER_POINT = 3, MTSG_EMITTER_SPOT = 4, MTSG_EMITTER_DIRECTIONAL = 5 };
 enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        MTSG_FEAT_DIFF = 8,     // DIFF: every BSDF is diffuse (path megakernel, FEAT 0 scenes only)
        // BSDF-set specialisation of the megakernel (dbsdf.h BSet): every rough
@@ -112,8 +114,13 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        MTSG_FEAT_GGX = 16, MTSG_FEAT_NORD = 32, MTSG_FEAT_NORC = 64,
        MTSG_FEAT_INL = 128,     // microfacet / Fresnel helpers inline (the wavefront per-type kernels)
        MTSG_FEAT_NOSTRICT = 256,     // megakernel BSDF-set variants: strictNormals off (render_plan.cpp picks the generic kernel otherwise)
-       MTSG_FEAT_NOREFN = 512 };     // BSDF-set variants of scenes lit by a (non-constant) envmap alone: no area
+       MTSG_FEAT_NOREFN = 512,       // BSDF-set variants of scenes lit by a (non-constant) envmap alone: no area
                                      // light and no constant emitter, so DirectSamplingRecord::refN is never read
+       // the scene has point / spot / directional emitters (ddelta.h).  Such scenes run one feature
+       // set of their own, ENV | EXT | ANA | DELTA, whatever else they hold: its kernels test at
+       // run time whether there is an environment (every other set's kernels know)
+       MTSG_FEAT_DELTA = 1024 };
+#define MTSG_FEAT_SET_DELTA (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA | MTSG_FEAT_DELTA)   // = 1031
 enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_DIRECT = 1, MTSG_INTEGRATOR_VOLPATH = 2 };   // = MTSGPU_INTEGRATOR_*
 enum { MTSG_SAMPLER_SOBOL = 0, MTSG_SAMPLER_INDEPENDENT = 1, MTSG_SAMPLER_SFMT_REPLAY = 2,
        MTSG_SAMPLER_SFMT_BLOCKS = 3 };    // = MTSGPU_SAMPLER_*
@@ -149,6 +156,17 @@ struct MtsgEmitter {
     uint32_t cdf_offset;             // into area_cdf (tri_count + 1 entries)
     float inv_area, weight, pad;
     float radiance[3], pad2;
+};
+
+// A delta emitter's configured record (emitters/point.cpp, spot.cpp, directional.cpp);
+// MtsgEmitter::tri_first of such an emitter is its index into MtsgDeviceScene::delta
+struct MtsgDelta {           // 80 B
+    float pos[3];            // point, spot: trafo.transformAffine(Point(0)); directional: the disk centre
+                             // m_bsphere.center - d * m_bsphere.radius (directional.cpp:162)
+    float dir[3];            // directional: d = trafo(Vector(0, 0, 1))
+    float to_local[9];       // spot: the vector part of trafo.inverse() (row-major)
+    float cos_beam, cos_cutoff, cutoff, inv_transition;   // spot: configure() (spot.cpp:89-94), radians
+    float radius;            // directional: m_bsphere.radius (the kd-tree AABB's sphere x 1.1)
 };
 
 struct MtsgCamera {
@@ -216,6 +234,7 @@ struct MtsgDeviceScene {
     const float *rtrans;        // roughplastic rough-transmittance slices (rtrans.h)
     const float *texcoords;     // 2 per vertex (textured scenes), else null
     const MtsgAnalytic *analytic;   // analytic shape records, or null
+    const MtsgDelta *delta;         // delta emitter records, or null
     uint32_t num_emitters, num_prims;
     float em_norm;
     int32_t env_emitter;        // index of the environment emitter, -1: none
@@ -303,6 +322,7 @@ struct MtsgLaunch {
     uint32_t ana;                     // kernel variant: analytic shapes present (implies ext)
     uint32_t all_diffuse;             // kernel variant: every BSDF is diffuse (MTSG_FEAT_DIFF)
     uint32_t bset;                    // the scene's MTSG_FEAT_GGX / NORD / NORC bits (render_plan.cpp plan_bset)
+    uint32_t delta;                   // kernel variant: delta emitters present (the MTSG_FEAT_SET_DELTA kernels)
     uint32_t xcds;                    // XCDs the device's CUs span (workgroup -> XCD remap; 1: none)
     // MTSGPU_FLAG_KDTREE (wavefront engine): wf_trace traverses the reference's kd-tree
     const uint32_t *kd_nodes;         // KDNode words (2 per node), null: the BVH

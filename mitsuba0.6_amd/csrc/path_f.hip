@@ -9,6 +9,8 @@
 // with an environment emitter also the 7 sets of envmap-only scenes (bit 3,
 // MTSG_FEAT_NOREFN: no area light, no constant emitter).
 // The set kernels are compiled without strictNormals (MTSG_FEAT_NOSTRICT).
+// PATH_FEAT 1031 (MTSG_FEAT_SET_DELTA) is the set of scenes with point / spot /
+// directional emitters: the generic kernel alone, with and without SCENE_LDS.
 #include "dmega.h"
 
 #define PF_NAME2(a, N) a##N
@@ -48,6 +50,7 @@ PathKernelFn pick_v(const MtsgLaunch &L, bool instr) {
 // (path_kernel.hip path_pick); bits: spec_bits
 PathKernelFn PF_NAME(mtsg_path_pick_f, PATH_FEAT)(const MtsgLaunch &L, int bits, bool instr) {
     switch (bits) {
+#if !(PATH_FEAT & 1024)   // MTSG_FEAT_DELTA: delta-emitter scenes run the generic kernel only (spec_bits gives 0)
         case 1: return pick_v<spec_feat(1)>(L, instr);
         case 2: return pick_v<spec_feat(2)>(L, instr);
         case 3: return pick_v<spec_feat(3)>(L, instr);
@@ -63,6 +66,7 @@ PathKernelFn PF_NAME(mtsg_path_pick_f, PATH_FEAT)(const MtsgLaunch &L, int bits,
         case 13: return pick_v<spec_feat(13)>(L, instr);
         case 14: return pick_v<spec_feat(14)>(L, instr);
         case 15: return pick_v<spec_feat(15)>(L, instr);
+#endif
 #endif
         default:
 #if PATH_FEAT == 0

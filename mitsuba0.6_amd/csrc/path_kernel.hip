@@ -71,18 +71,27 @@ __device__ __forceinline__ f3 env_camera(const MtsgLaunch &L, float sx, float sy
 
 // Scene::sampleEmitterDirect without the visibility test (scene.cpp:828-852):
 // value = radiance / (pdf * emPdf) and pdf = dRec.pdf * emPdf when pdf != 0
-struct NeeSample { f3 value, d; float dist, pdf; };
-template <bool ENV, bool ANA, typename HS>
+// delta: the sample is a delta emitter's (ddelta.h; Emitter::isOnSurface() false: direct.cpp:235)
+struct NeeSample { f3 value, d; float dist, pdf; bool delta; };
+template <bool ENV, bool ANA, bool DELTA = false, typename HS>
 __device__ __forceinline__ NeeSample emitter_sample(const MtsgDeviceScene &S, const HS &hs, f3 ref, f3 refN, float ex,
                                                     float ey) {
     NeeSample r;
-    r.value = mk(0, 0, 0); r.d = mk(0, 0, 1); r.dist = 0.0f; r.pdf = 0.0f;
+    r.value = mk(0, 0, 0); r.d = mk(0, 0, 1); r.dist = 0.0f; r.pdf = 0.0f; r.delta = false;
     float emPdf;
     const uint32_t ei = dd_sample_reuse(S.em_cdf, S.num_emitters, ex, &emPdf);
     const MtsgEmitter &e = S.emitters[ei];
     f3 value = mk(0, 0, 0);
     float pdf = 0.0f;
-    if (ENV && e.type != MTSG_EMITTER_AREA) {
+    bool isDelta = false;
+    if constexpr (DELTA) isDelta = e.type >= MTSG_EMITTER_POINT;
+    if (DELTA && isDelta) {
+        if constexpr (DELTA) {
+            const DeltaSample ds = delta_sample_direct(e.type, ((GDelta *)S.delta)[e.tri_first], ld3(e.radiance), ref);
+            value = ds.value; r.d = ds.d; r.dist = ds.dist; pdf = ds.pdf;
+            r.delta = true;
+        }
+    } else if (ENV && e.type != MTSG_EMITTER_AREA) {
         glb_env *E = (glb_env *)S.env;
         const EnvSample es = E->constant ? const_sample_direct(E, ref, refN, ex, ey) : env_sample_direct(E, ref, ex, ey);
         value = es.value; r.d = es.d; r.dist = es.dist; pdf = es.pdf;
@@ -202,9 +211,11 @@ SHADOW_ANY_CALL bool shadow_any(NodeT *nodes, TriT *tris, f3 o, f3 d, float mint
 template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLaunch L) {
     constexpr bool ENV = (FEAT & MTSG_FEAT_ENV) != 0, EXT = (FEAT & MTSG_FEAT_EXT) != 0,
-                   ANA = (FEAT & MTSG_FEAT_ANA) != 0;
+                   ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0;
     extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
+    // the delta-emitter feature set is compiled with ENV; its scenes need not have an environment
+    const bool haveEnv = !DELTA || S.env_emitter >= 0;
     // LDS as path_kernel: [Sobol nibble tables][look_up tables][scene (small scenes)][stacks]
     const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
     lds_u32 *ycolTab = V.ycolTab;
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
         const bool hit = closest(ro, rd, rmint, rmaxt, its);
         const float alpha = L.has_alpha ? (hit ? 1.0f : 0.0f) : 1.0f;
         if (!hit) {
-            if (ENV && !L.hide_emitters) Li = env_camera(L, sx, sy, rd);
+            if (ENV && haveEnv && !L.hide_emitters) Li = env_camera(L, sx, sy, rd);
         } else {
             auto &sh = hs.shapes[its.shape];
             GBsdf &bsdf = ((GBsdf *)S.bsdfs)[sh.bsdf];
@@ -297,7 +308,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                         if (L.lum_samples > 1)
                             sobol_array2d(SC, L.lut, ycolTab, L.nibbles, j, L.lum_samples, i, px, py, L.scramble64,
                                           L.lum_dim, nx, ny);
-                        NeeSample ns = emitter_sample<ENV, ANA>(S, hs, its.p, refN, nx, ny);
+                        NeeSample ns = emitter_sample<ENV, ANA, DELTA>(S, hs, its.p, refN, nx, ny);
                         if (ns.pdf != 0 && occluded(its.p, ns.d, ns.dist)) ns.value = mk(0, 0, 0);
                         if (ns.pdf == 0) ns.value = mk(0, 0, 0);
                         if (!is_zero(ns.value)) {
@@ -306,6 +317,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                             float bsdfPdf;
                             bsdf_eval_pdf_2s<EXT>(S, bsdf, its, wo, bsdfVal, &bsdfPdf);
                             if (!is_zero(bsdfVal) && (!L.strict_normals || dot(its.geoN, ns.d) * wo.z > 0)) {
+                                if (DELTA && ns.delta) bsdfPdf = 0.0f;   // emitter->isOnSurface() ? bsdf->pdf(bRec) : 0
                                 const float pa = ns.pdf * L.frac_lum, pb = bsdfPdf * L.frac_bsdf;
                                 const float weight = (pa * pa) / (pa * pa + pb * pb) * L.weight_lum;
                                 Li = add(Li, mul(mulv(ns.value, bsdfVal), weight));
@@ -334,7 +346,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                         value = area_Le(S, h2, neg(wo));
                         if (!(bs.sampledType & MTSG_F_DELTA)) lumPdf = area_hit_pdf<ANA>(S, h2, its.p, wo, refN);
                     } else {
-                        if (!ENV || (L.hide_emitters && bs.sampledType == MTSG_F_NULL)) continue;
+                        if (!ENV || !haveEnv || (L.hide_emitters && bs.sampledType == MTSG_F_NULL)) continue;
                         glb_env *E = (glb_env *)S.env;
                         value = E->constant ? mk(E->radiance[0], E->radiance[1], E->radiance[2]) : env_eval(E, wo);
                         float nT, fT;
@@ -695,6 +707,7 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
 bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L); }
 
 int mtsg_path_features(const MtsgLaunch &L) {
+    if (L.delta) return MTSG_FEAT_SET_DELTA;   // delta-emitter scenes: the one set that holds everything
     return (L.scene.env_emitter >= 0 ? MTSG_FEAT_ENV : 0) | ((L.ext || L.ana) ? MTSG_FEAT_EXT : 0) |
            (L.ana ? MTSG_FEAT_ANA : 0);
 }
@@ -704,7 +717,7 @@ int mtsg_path_features(const MtsgLaunch &L) {
 // (render_plan.cpp plan_render, L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
 // small scenes staged in LDS and the direct integrator take the generic kernel.
 static int spec_bits(const MtsgLaunch &L) {
-    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT) return 0;
+    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta) return 0;   // (delta: the generic set only)
     const int b = ((L.bset & MTSG_FEAT_GGX) ? 1 : 0) | ((L.bset & MTSG_FEAT_NORD) ? 2 : 0) | ((L.bset & MTSG_FEAT_NORC) ? 4 : 0);
     return b | ((b && (L.bset & MTSG_FEAT_NOREFN) && (mtsg_path_features(L) & MTSG_FEAT_ENV)) ? 8 : 0);
 }
@@ -719,6 +732,7 @@ static PathKernelFn path_pick(const MtsgLaunch &L, bool instr) {
         case MTSG_FEAT_EXT: return mtsg_path_pick_f2(L, bits, instr);
         case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_path_pick_f3(L, bits, instr);
         case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_pick_f6(L, bits, instr);
+        case MTSG_FEAT_SET_DELTA: return mtsg_path_pick_f1031(L, bits, instr);
         default: return mtsg_path_pick_f7(L, bits, instr);
     }
 }
@@ -739,6 +753,7 @@ hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool st
             case MTSG_FEAT_EXT: launch_direct<MTSG_FEAT_EXT>(L, grid, stream); break;
             case MTSG_FEAT_ENV | MTSG_FEAT_EXT: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT>(L, grid, stream); break;
             case MTSG_FEAT_EXT | MTSG_FEAT_ANA: launch_direct<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
+            case MTSG_FEAT_SET_DELTA: launch_direct<MTSG_FEAT_SET_DELTA>(L, grid, stream); break;
             default: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
         }
         return hipGetLastError();

@@ -164,7 +164,7 @@ uint32_t plan_bset(const HostScene &H, const mtsgpu_render_params &P, const Rend
     float extent = 0.0f;
     for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs(H.aabb_min[a]), std::fabs(H.aabb_max[a])));
     // (the set kernels are built without strictNormals: MTSG_FEAT_NOSTRICT)
-    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals) ? 0u
+    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals || !H.deltas.empty()) ? 0u
                     : (ggx ? (uint32_t)MTSG_FEAT_GGX : 0u) | (rc ? 0u : (uint32_t)MTSG_FEAT_NORC) |
                           (rd ? 0u : (uint32_t)MTSG_FEAT_NORD);
     // envmap-only scenes (no area light, no constant emitter): the set kernels without
@@ -186,7 +186,9 @@ void plan_variant(MtsgLaunch &L, const HostScene &H, const mtsgpu_render_params 
     L.scan = (L.scene_lds && H.tris.size() <= MTSG_SCAN_MAX && H.analytic.empty() && !K.no_scan) ? 1u : 0u;
     L.ext = H.ext ? 1u : 0u;
     L.ana = H.analytic.empty() ? 0u : 1u;
-    L.all_diffuse = K.no_diff_variant ? 0u : 1u;
+    // point / spot / directional emitters: the MTSG_FEAT_SET_DELTA kernels, the generic BSDF set only
+    L.delta = H.deltas.empty() ? 0u : 1u;
+    L.all_diffuse = (K.no_diff_variant || L.delta) ? 0u : 1u;
     for (const MtsgBsdf &b : H.bsdfs) L.all_diffuse &= b.type == MTSGPU_BSDF_DIFFUSE ? 1u : 0u;
     L.bset = plan_bset(H, P, K);
     // large scenes are latency-bound: run 4 waves/SIMD when 4 blocks' traversal
@@ -459,14 +461,17 @@ WfPlan plan_wavefront(const RenderPlan &plan, const HostScene &H, const RenderKn
 
 // counter 15: which kernel ran -- for the megakernel path_kernel<INSTR, SCENE_LDS, FEAT, WAVES>:
 // FEAT's low 8 bits | WAVES << 8 | SCENE_LDS << 12 | INSTR << 13 | (FEAT & NOSTRICT) << 14 (the
-// set kernels' strictNormals-free build) | (FEAT & NOREFN) << 15; 1 << 16 for the wavefront engine
+// set kernels' strictNormals-free build) | (FEAT & NOREFN) << 15; 1 << 16 for the wavefront engine;
+// 1 << 18 (MTSGPU_VARIANT_DELTA) on top of any of these: the MTSG_FEAT_SET_DELTA instantiations of
+// scenes with delta emitters -- the megakernel, direct_kernel or the wavefront shade kernels
 // (tests and A/B logs read it)
 uint64_t plan_variant_word(const RenderPlan &plan) {
     const MtsgLaunch &L = plan.L;
-    if (plan.engine == MTSG_ENGINE_WAVEFRONT) return 1ull << 16;
+    const uint64_t dbit = L.delta ? 1ull << 18 : 0;
+    if (plan.engine == MTSG_ENGINE_WAVEFRONT) return (1ull << 16) | dbit;
     if (plan.engine == MTSG_ENGINE_FIELDS)   // field_kernel<SCENE_LDS, ..>: 1 << 17 | SCENE_LDS << 12
         return (1ull << 17) | ((uint64_t)L.scene_lds << 12);
     const int v = mtsg_path_variant(L);
-    return (uint64_t)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) | (plan.instr ? 1 << 13 : 0) |
+    return dbit | (uint64_t)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) | (plan.instr ? 1 << 13 : 0) |
                       ((v & MTSG_FEAT_NOSTRICT) ? 1 << 14 : 0) | ((v & MTSG_FEAT_NOREFN) ? 1 << 15 : 0));
 }

@@ -1053,6 +1053,66 @@ void envmap_bsphere(HostScene &S, const mtsgpu_sensor_desc &sensor) {
     S.env.radius = fmax_std(1e-4f, radius * 1.5f);
 }
 
+// ---- delta emitters (emitters/point.cpp, spot.cpp, directional.cpp) ----------
+// what the constructors and configure() derive from the emitter's transform; the
+// directional emitter's disk waits for the scene bounds (directional_bsphere)
+int configure_delta(const mtsgpu_emitter_desc &e, MtsgDelta &o, std::string &err) {
+    std::memset(&o, 0, sizeof o);
+    M4 T, Ti;
+    bool haveInv = false;
+    for (int i = 0; i < 16; ++i) {
+        T.m[i / 4][i % 4] = e.env_to_world[i];
+        Ti.m[i / 4][i % 4] = e.env_to_world_inv[i];
+        haveInv |= e.env_to_world_inv[i] != 0.0f;
+    }
+    if (!haveInv && !invert(T, Ti)) { err = "Singular matrix in Matrix::invert"; return MTSGPU_EINVAL; }
+    if (e.type == MTSGPU_EMITTER_DIRECTIONAL) {
+        // Transform::hasScale (transform.h:76-90), directional.cpp:69-71
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j) {
+                float sum = 0;
+                for (int k = 0; k < 3; ++k) sum += T.m[i][k] * T.m[j][k];
+                if (i == j ? std::fabs(sum - 1) > 1e-3f : std::fabs(sum) > 1e-3f) {
+                    err = "Scale factors in the emitter-to-world transformation are not allowed!";
+                    return MTSGPU_EINVAL;
+                }
+            }
+        const V d = xf_vec(T, v(0.0f, 0.0f, 1.0f));
+        o.dir[0] = d.x; o.dir[1] = d.y; o.dir[2] = d.z;
+        return MTSGPU_OK;
+    }
+    // trafo.transformAffine(Point(0)) (transform.h:109-121)
+    const V p = v(T.m[0][0] * 0.0f + T.m[0][1] * 0.0f + T.m[0][2] * 0.0f + T.m[0][3],
+                  T.m[1][0] * 0.0f + T.m[1][1] * 0.0f + T.m[1][2] * 0.0f + T.m[1][3],
+                  T.m[2][0] * 0.0f + T.m[2][1] * 0.0f + T.m[2][2] * 0.0f + T.m[2][3]);
+    o.pos[0] = p.x; o.pos[1] = p.y; o.pos[2] = p.z;
+    if (e.type == MTSGPU_EMITTER_SPOT) {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) o.to_local[3 * r + c] = Ti.m[r][c];
+        // SpotEmitter(props), configure() (spot.cpp:68-94): float cosf
+        const float beam = deg2rad(e.beam_width), cutoff = deg2rad(e.cutoff_angle);
+        if (!(cutoff >= beam)) { err = "Assertion 'm_cutoffAngle >= m_beamWidth' failed"; return MTSGPU_EINVAL; }
+        o.cos_beam = std::cos(beam);
+        o.cos_cutoff = std::cos(cutoff);
+        o.cutoff = cutoff;
+        o.inv_transition = 1.0f / (cutoff - beam);
+    }
+    return MTSGPU_OK;
+}
+
+// DirectionalEmitter::createShape (directional.cpp:88-94): the kd-tree AABB's bounding
+// sphere (aabb.cpp:44-47), radius x 1.1; the disk centre of sampleDirect (:162)
+void directional_bsphere(const HostScene &S, MtsgDelta &o) {
+    const V mx = v(S.aabb_max[0], S.aabb_max[1], S.aabb_max[2]), mn = v(S.aabb_min[0], S.aabb_min[1], S.aabb_min[2]);
+    const V center = (mx + mn) * 0.5f;
+    float radius = length(center - mx);
+    radius *= 1.1f;
+    const V d = v(o.dir[0], o.dir[1], o.dir[2]);
+    const V disk = center - d * radius;
+    o.pos[0] = disk.x; o.pos[1] = disk.y; o.pos[2] = disk.z;
+    o.radius = radius;
+}
+
 }  // namespace
 
 // ---- Sobol ------------------------------------------------------------------
@@ -1257,6 +1317,12 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
             S.env.emitter = (int)i;
             S.env.constant = 1;
             for (int k = 0; k < 3; ++k) S.env.radiance[k] = e.radiance[k];
+        } else if (e.type == MTSGPU_EMITTER_POINT || e.type == MTSGPU_EMITTER_SPOT ||
+                   e.type == MTSGPU_EMITTER_DIRECTIONAL) {
+            o.tri_first = (uint32_t)S.deltas.size();
+            MtsgDelta dl;
+            if ((rc = configure_delta(e, dl, err))) return rc;
+            S.deltas.push_back(dl);
         } else if (e.type != MTSGPU_EMITTER_AREA) {
             err = "unsupported emitter type";
             return MTSGPU_EINVAL;
@@ -1529,6 +1595,8 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
         S.aabb_min[a] = amin[a]; S.aabb_max[a] = amax[a];
     }
     if (S.env.emitter >= 0) envmap_bsphere(S, D->sensor);
+    for (const MtsgEmitter &e : S.emitters)
+        if (e.type == MTSGPU_EMITTER_DIRECTIONAL) directional_bsphere(S, S.deltas[e.tri_first]);
     // BVH
     Builder B(bp, S.nodes);
     B.order.resize(prims);

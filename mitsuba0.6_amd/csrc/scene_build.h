@@ -36,6 +36,7 @@ struct HostScene {
     std::vector<MtsgShape> shapes;
     std::vector<MtsgBsdf> bsdfs;
     std::vector<MtsgEmitter> emitters;
+    std::vector<MtsgDelta> deltas;   // point / spot / directional records (MtsgEmitter::tri_first indexes them)
     std::vector<float> area_cdf, em_cdf;
     float em_norm = 0;
     float aabb_min[3], aabb_max[3];

@@ -202,7 +202,11 @@ __device__ __forceinline__ void wf_shade_block(const MtsgLaunch &L, const MtsgWa
                 const float4 h = W.hit[s];
                 const uint32_t w = __float_as_uint(h.w);
                 ht = h.x; hu = h.y; hv = h.z;
-                if ((FEAT & MTSG_FEAT_ANA) != 0) { slot = w; prim = S.tris[slot].prim; }
+                // (the delta-emitter set is compiled with ANA whatever the scene holds, while the
+                // trace kernel follows the scene, L.ana: without analytic shapes the word is the
+                // primitive, and fill_hit's look at slot 0 finds a triangle record)
+                constexpr bool ANAF = (FEAT & MTSG_FEAT_ANA) != 0, DELTAF = (FEAT & MTSG_FEAT_DELTA) != 0;
+                if (ANAF && (!DELTAF || L.ana)) { slot = w; prim = S.tris[slot].prim; }
                 else prim = w;
             }
         }

@@ -16,6 +16,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import abi
+from .transform import Transform, _normalize, coordinate_system, deg_to_rad, transform_has_scale
 
 # IOR table entries used by the configs (src/bsdfs/ior.h:40-67)
 IOR = {'vacuum': 1.0, 'air': 1.000277, 'water': 1.3330, 'bk7': 1.5046, 'glass': 1.5046,
@@ -165,20 +166,71 @@ class Emitter:
 
     envmap: `bitmap` is the decoded lat-long image, (H, W, 3) linear RGB float32
     (what Bitmap(EAuto, stream) yields for an RGB EXR/PFM/HDR file), `scale` and
-    `toWorld` (a transform.Transform) as in the XML."""
+    `toWorld` (a transform.Transform) as in the XML.
+
+    The delta emitters `point` (src/emitters/point.cpp: `intensity`, `position` xor
+    `toWorld`), `spot` (spot.cpp: `intensity`, `toWorld`, `cutoffAngle` and `beamWidth`
+    in degrees; no projection texture) and `directional` (directional.cpp: `irradiance`,
+    `direction` xor `toWorld`, which must not scale).  `position` and `direction` become
+    the transform the plugins build, in float32: Transform::translate, and
+    Transform::lookAt(0, d, u) with u from coordinateSystem(normalize(direction)).
+    Spectrum::getD65() is 1 in the RGB build, so every default intensity is 1."""
     type: str = 'area'
     radiance: tuple = (1.0, 1.0, 1.0)
     samplingWeight: float = 1.0
     bitmap: Optional[np.ndarray] = None
     scale: float = 1.0
     toWorld: object = None
+    intensity: Optional[tuple] = None      # point, spot
+    irradiance: Optional[tuple] = None     # directional
+    position: Optional[tuple] = None       # point
+    direction: Optional[tuple] = None      # directional
+    cutoffAngle: float = 20.0              # spot (spot.cpp:70-71)
+    beamWidth: Optional[float] = None      # spot: 3/4 cutoffAngle
+
+    TYPES = {'area': abi.EMITTER_AREA, 'envmap': abi.EMITTER_ENVMAP, 'constant': abi.EMITTER_CONSTANT,
+             'point': abi.EMITTER_POINT, 'spot': abi.EMITTER_SPOT, 'directional': abi.EMITTER_DIRECTIONAL}
+    DELTA = ('point', 'spot', 'directional')
+
+    def __post_init__(self):
+        if self.type not in self.TYPES:
+            raise ValueError('emitter type "%s"' % self.type)
+        f32 = np.float32
+        if self.type == 'point' and self.position is not None:          # point.cpp:60-66
+            if self.toWorld is not None:
+                raise ValueError("Only one of the parameters 'position' and 'toWorld' can be used!'")
+            self.toWorld = Transform.translate_(*[f32(x) for x in self.position])
+        if self.type == 'directional':                                   # directional.cpp:59-72
+            if self.direction is not None:
+                if self.toWorld is not None:
+                    raise ValueError("Only one of the parameters 'direction' and 'toWorld'can be used at a time!")
+                d = _normalize(np.asarray(self.direction, f32))
+                u = coordinate_system(d)[0]
+                self.toWorld = Transform.look_at_((0.0, 0.0, 0.0), d, u)
+            elif self.toWorld is not None and transform_has_scale(self.toWorld):
+                raise ValueError('Scale factors in the emitter-to-world transformation are not allowed!')
+        if self.type == 'spot':                                          # spot.cpp:70-74
+            if self.beamWidth is None:
+                self.beamWidth = float(f32(f32(self.cutoffAngle) * f32(f32(3.0) / f32(4.0))))
+            if not (deg_to_rad(self.cutoffAngle) >= deg_to_rad(self.beamWidth)):
+                raise ValueError("Assertion 'm_cutoffAngle >= m_beamWidth' failed")
+        if self.type in self.DELTA:
+            v = self.irradiance if self.type == 'directional' else self.intensity
+            if v is not None:
+                self.radiance = tuple(float(x) for x in v)
+            if self.type == 'directional':
+                self.irradiance = tuple(self.radiance)
+            else:
+                self.intensity = tuple(self.radiance)
 
     def to_desc(self):
         d = abi.EmitterDesc()
-        d.type = {'area': abi.EMITTER_AREA, 'envmap': abi.EMITTER_ENVMAP, 'constant': abi.EMITTER_CONSTANT}[self.type]
+        d.type = self.TYPES[self.type]
         d.radiance[:] = self.radiance
         d.sampling_weight = self.samplingWeight
         d.env_scale = self.scale
+        if self.type == 'spot':
+            d.cutoff_angle, d.beam_width = self.cutoffAngle, self.beamWidth
         if self.toWorld is not None:
             d.env_to_world[:] = [float(x) for x in np.asarray(self.toWorld.m, np.float32).reshape(-1)]
             d.env_to_world_inv[:] = [float(x) for x in np.asarray(self.toWorld.inv, np.float32).reshape(-1)]

@@ -52,6 +52,36 @@ def _cross(a, b):
                      f32(a[0] * b[1]) - f32(a[1] * b[0])], f32)
 
 
+def coordinate_system(a):
+    """coordinateSystem(a, b, c) (util.cpp:592-601) in float32: returns (b, c)."""
+    a = np.asarray(a, f32)
+    if abs(a[0]) > abs(a[1]):
+        inv_len = f32(f32(1) / f32(np.sqrt(f32(f32(a[0] * a[0]) + f32(a[2] * a[2])))))
+        c = np.array([f32(a[2] * inv_len), f32(0), f32(-a[0] * inv_len)], f32)
+    else:
+        inv_len = f32(f32(1) / f32(np.sqrt(f32(f32(a[1] * a[1]) + f32(a[2] * a[2])))))
+        c = np.array([f32(0), f32(a[2] * inv_len), f32(-a[1] * inv_len)], f32)
+    return _cross(c, a), c
+
+
+def deg_to_rad(x):
+    """degToRad (util.h:297) in float32."""
+    return f32(f32(x) * f32(f32(np.pi) / f32(180)))
+
+
+def transform_has_scale(t):
+    """Transform::hasScale (transform.h:76-90)."""
+    m = np.asarray(t.m, f32)
+    for i in range(3):
+        for j in range(i, 3):
+            s = f32(0)
+            for k in range(3):
+                s = f32(s + f32(m[i, k] * m[j, k]))
+            if (i == j and abs(f32(s - f32(1))) > f32(1e-3)) or (i != j and abs(s) > f32(1e-3)):
+                return True
+    return False
+
+
 class Transform:
     def __init__(self, m=None, inv=None):
         self.m = np.eye(4, dtype=f32) if m is None else np.asarray(m, f32).copy()

@@ -26,7 +26,8 @@ Plugins:
   `rectangle`, `disk`, `sphere`.
 - BSDFs `diffuse`, `roughconductor`, `roughdielectric`, `roughplastic`,
   `conductor`, `dielectric`, `plastic`, `twosided`; `checkerboard` textures.
-- emitters `area` (inside a shape), `envmap` (PFM/EXR/RGBE files) and `constant`.
+- emitters `area` (inside a shape), `envmap` (PFM/EXR/RGBE files), `constant`, and the delta
+  emitters `point`, `spot` (no projection texture) and `directional` at scene level.
 
 Anything else raises NotImplementedError naming the plugin (e.g. `cylinder`,
 `hair`, media).
@@ -340,7 +341,29 @@ class XMLSceneLoader:
             raise NotImplementedError('shape-attached emitter "%s"' % p.plugin)
         return Emitter('area', radiance=p.get('radiance', (1.0, 1.0, 1.0)), samplingWeight=p.get('samplingWeight', 1.0))
 
+    def make_delta(self, p):
+        """point.cpp:57-69, spot.cpp:68-78, directional.cpp:55-73; Spectrum::getD65() is 1 in the RGB build."""
+        w = float(p.get('samplingWeight', 1.0))
+        try:
+            if p.plugin == 'point':
+                return Emitter('point', intensity=p.get('intensity', (1.0, 1.0, 1.0)), position=p.get('position'),
+                               toWorld=p.get('toWorld'), samplingWeight=w)
+            if p.plugin == 'directional':
+                return Emitter('directional', irradiance=p.get('irradiance', (1.0, 1.0, 1.0)),
+                               direction=p.get('direction'), toWorld=p.get('toWorld'), samplingWeight=w)
+            for _, c in p.children:   # a projection texture (spot.cpp:112-118)
+                raise NotImplementedError('spot: <%s> child (projection textures are not on the GPU path)' % c.tag)
+            if 'texture' in p:
+                raise NotImplementedError('spot: a "texture" spectrum other than the default')
+            return Emitter('spot', intensity=p.get('intensity', (1.0, 1.0, 1.0)), toWorld=p.get('toWorld'),
+                           cutoffAngle=float(p.get('cutoffAngle', 20.0)),
+                           beamWidth=float(p['beamWidth']) if 'beamWidth' in p else None, samplingWeight=w)
+        except ValueError as e:
+            raise SceneError(str(e))
+
     def make_envmap(self, p):
+        if p.plugin in Emitter.DELTA:
+            return self.make_delta(p)
         if p.plugin == 'constant':   # constant.cpp:46-49; Spectrum::getD65() is 1 in the RGB build (spectrum.cpp:163-165)
             return Emitter('constant', radiance=p.get('radiance', (1.0, 1.0, 1.0)),
                            samplingWeight=float(p.get('samplingWeight', 1.0)))
@@ -415,9 +438,9 @@ class XMLSceneLoader:
                 self.parse_object(el)       # named object for later <ref>
             elif el.tag == 'emitter':
                 p = self.parse_object(el)
-                if p.plugin not in ('envmap', 'constant'):
-                    raise NotImplementedError('emitter plugin "%s" (area lights on shapes, envmap and constant '
-                                              'are supported)' % p.plugin)
+                if p.plugin not in ('envmap', 'constant') + Emitter.DELTA:
+                    raise NotImplementedError('emitter plugin "%s" (area lights on shapes, envmap, constant, '
+                                              'point, spot and directional are supported)' % p.plugin)
                 env_props.append(p)
             elif el.tag in ('medium', 'subsurface'):
                 raise NotImplementedError('<%s>: participating media / subsurface are not on the path' % el.tag)
@@ -465,7 +488,8 @@ class XMLSceneLoader:
                     mesh.emitter = len(emitters)
                     emitters.append(self.make_area(c))
                 meshes.append(mesh)
-        # the environment emitter comes after the shapes' emitters (Scene::addChild order)
+        # the scene-level emitters (environment, point, spot, directional), in document order, come
+        # after the shapes' emitters (Scene::addChild order)
         for ep in env_props:
             emitters.append(self.make_envmap(ep))
         if not meshes:
@@ -823,6 +847,18 @@ def save_scene(scene, integ, directory, name='scene.xml'):
         if e.type == 'constant':
             L.append('  <emitter type="constant">%s<float name="samplingWeight" value="%s"/></emitter>'
                      % (_rgb('radiance', e.radiance), _fmt(e.samplingWeight)))
+            continue
+        if e.type in Emitter.DELTA:
+            L.append('  <emitter type="%s">' % e.type)
+            L.append('    ' + _rgb('irradiance' if e.type == 'directional' else 'intensity', e.radiance))
+            L.append('    <float name="samplingWeight" value="%s"/>' % _fmt(e.samplingWeight))
+            if e.type == 'spot':
+                L.append('    <float name="cutoffAngle" value="%s"/>' % _fmt(e.cutoffAngle))
+                L.append('    <float name="beamWidth" value="%s"/>' % _fmt(e.beamWidth))
+            # position / direction were turned into toWorld when the emitter was made
+            if e.toWorld is not None:
+                L.append('    <transform name="toWorld">%s</transform>' % _transform_xml(e.toWorld))
+            L.append('  </emitter>')
             continue
         if e.type != 'envmap':
             continue
