@@ -168,12 +168,23 @@ typedef struct {
 enum { MTSGPU_FOV_X = 0, MTSGPU_FOV_Y = 1, MTSGPU_FOV_DIAGONAL = 2,
        MTSGPU_FOV_SMALLER = 3, MTSGPU_FOV_LARGER = 4 };
 
-typedef struct {                    /* perspective.cpp + librender/sensor.cpp      */
-    float fov;                      /* degrees                                     */
+enum { /* sensor plugins (src/sensors): the projective cameras */
+    MTSGPU_SENSOR_PERSPECTIVE = 0,   /* perspective.cpp                                      */
+    MTSGPU_SENSOR_THINLENS = 1,      /* thinlens.cpp: perspective + aperture, focus plane    */
+    MTSGPU_SENSOR_ORTHOGRAPHIC = 2,  /* orthographic.cpp: no fov; 'toWorld' may carry scale  */
+    MTSGPU_SENSOR_TELECENTRIC = 3    /* telecentric.cpp: orthographic + aperture, focus plane */
+};
+
+typedef struct {                    /* src/sensors + librender/sensor.cpp          */
+    float fov;                      /* degrees (perspective, thinlens)             */
     int32_t fov_axis;               /* MTSGPU_FOV_*                                */
     float near_clip, far_clip;      /* defaults 1e-2, 1e4                          */
     float to_world[16];             /* row-major camera-to-world                   */
     uint32_t film_width, film_height;
+    /* appended (the struct is the last member of mtsgpu_scene_desc: no offset moved) */
+    int32_t type;                   /* MTSGPU_SENSOR_*                             */
+    float aperture_radius;          /* thinlens (0 becomes Epsilon), telecentric   */
+    float focus_distance;           /* thinlens, telecentric (default: far_clip)   */
 } mtsgpu_sensor_desc;
 
 typedef struct {

@@ -172,10 +172,19 @@ public:
            (perspective.cpp:474) under the abstract PerspectiveCamera (sensor.cpp:319);
            'perspective_rdist' (PerspectiveCameraRDist, perspective_rdist.cpp:556) derives
            from it too but adds lens distortion, which the library does not model. */
-        if (!sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera))
-            || sensor->getClass()->getName() != "PerspectiveCameraImpl")
-            Log(EError, "only the 'perspective' sensor is supported (got %s)",
-                sensor->getClass()->getName().c_str());
+        /* The other projective cameras: 'thinlens' (ThinLens, a PerspectiveCamera too),
+           'orthographic' (OrthographicCamera) and 'telecentric' (TelecentricLensCamera). */
+        const std::string sensName = sensor->getClass()->getName();
+        const bool perspLike = sensName == "PerspectiveCameraImpl" || sensName == "ThinLens";
+        if (!sensor->getClass()->derivesFrom(MTS_CLASS(ProjectiveCamera))
+            || (perspLike && !sensor->getClass()->derivesFrom(MTS_CLASS(PerspectiveCamera)))
+            || (!perspLike && sensName != "OrthographicCamera" && sensName != "TelecentricLensCamera"))
+            Log(EError, "the 'perspective', 'thinlens', 'orthographic' and 'telecentric' sensors are "
+                "supported (got %s)", sensName.c_str());
+        /* getShutterOpenTime() is the shutter's duration, shutterClose - shutterOpen (sensor.cpp):
+           the new sensors draw no time sample.  'perspective' is handled as it always was. */
+        if (sensName != "PerspectiveCameraImpl" && sensor->getShutterOpenTime() != 0)
+            Log(EError, "shutterOpen != shutterClose: motion blur is not supported");
 #if GPU_INTEGRATOR == 1
         if (sensor->getMedium())
             Log(EError, "gpuvolpath: participating media are not supported");
@@ -286,9 +295,20 @@ public:
         sd.bsdfs = m_bsdfs.data(); sd.num_bsdfs = (uint32_t) m_bsdfs.size();
         sd.emitters = emitters.data(); sd.num_emitters = (uint32_t) emitters.size();
         /* perspective.cpp: the derived x field of view, clip planes, camera-to-world */
-        const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor.get());
-        sd.sensor.fov = (float) cam->getXFov();
-        sd.sensor.fov_axis = MTSGPU_FOV_X;
+        const ProjectiveCamera *cam = static_cast<const ProjectiveCamera *>(sensor.get());
+        if (perspLike) {
+            sd.sensor.fov = (float) static_cast<const PerspectiveCamera *>(sensor.get())->getXFov();
+            sd.sensor.fov_axis = MTSGPU_FOV_X;
+        }
+        sd.sensor.type = sensName == "ThinLens" ? MTSGPU_SENSOR_THINLENS
+                       : sensName == "OrthographicCamera" ? MTSGPU_SENSOR_ORTHOGRAPHIC
+                       : sensName == "TelecentricLensCamera" ? MTSGPU_SENSOR_TELECENTRIC : MTSGPU_SENSOR_PERSPECTIVE;
+        if (sd.sensor.type == MTSGPU_SENSOR_THINLENS || sd.sensor.type == MTSGPU_SENSOR_TELECENTRIC) {
+            /* thinlens.cpp:132, telecentric.cpp:81: the property (the plugins keep it private);
+               the library turns thinlens' 0 into Epsilon as the constructor does */
+            sd.sensor.aperture_radius = (float) sensor->getProperties().getFloat("apertureRadius", 0.0f);
+            sd.sensor.focus_distance = (float) cam->getFocusDistance();
+        }
         sd.sensor.near_clip = (float) cam->getNearClip();
         sd.sensor.far_clip = (float) cam->getFarClip();
         copyMatrix(sensor->getWorldTransform()->eval(0).getMatrix(), sd.sensor.to_world);

@@ -21,6 +21,7 @@ EMITTER_AREA, EMITTER_ENVMAP, EMITTER_CONSTANT = 0, 1, 2
 EMITTER_POINT, EMITTER_SPOT, EMITTER_DIRECTIONAL = 3, 4, 5
 SHAPE_TRIMESH, SHAPE_RECTANGLE, SHAPE_DISK, SHAPE_SPHERE = 0, 1, 2, 3
 FOV_X, FOV_Y, FOV_DIAGONAL, FOV_SMALLER, FOV_LARGER = 0, 1, 2, 3, 4
+SENSOR_PERSPECTIVE, SENSOR_THINLENS, SENSOR_ORTHOGRAPHIC, SENSOR_TELECENTRIC = 0, 1, 2, 3
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 INTEGRATOR_PATH, INTEGRATOR_DIRECT, INTEGRATOR_VOLPATH = 0, 1, 2
 SAMPLER_SOBOL, SAMPLER_INDEPENDENT, SAMPLER_SFMT_REPLAY, SAMPLER_SFMT_BLOCKS = 0, 1, 2, 3
@@ -75,7 +76,8 @@ class MeshDesc(C.Structure):
 class SensorDesc(C.Structure):
     _fields_ = [('fov', C.c_float), ('fov_axis', C.c_int32), ('near_clip', C.c_float),
                 ('far_clip', C.c_float), ('to_world', _f16),
-                ('film_width', C.c_uint32), ('film_height', C.c_uint32)]
+                ('film_width', C.c_uint32), ('film_height', C.c_uint32),
+                ('type', C.c_int32), ('aperture_radius', C.c_float), ('focus_distance', C.c_float)]
 
 
 class SceneDesc(C.Structure):

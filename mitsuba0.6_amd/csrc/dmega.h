@@ -88,7 +88,11 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     // its unit: 32 bits, not a 64-bit item index, live across the bounce loop)
     // Kernels with the start queue: `round` and prodPix are the lane's PRODUCER state (its
     // item stream, unchanged); st.pix belongs to whatever path the lane renders
-    constexpr bool QUEUE = SCENE_LDS && MTSG_START_QUEUE;
+    // (not the MTSG_FEAT_LENS kernels: their start record is three origin words and an
+    // interval longer, and the aperture draw would run beside every lane's live path state;
+    // mtsg_path_start_queue says the same of their launches.  They start as the kernels
+    // without the queue do, holding a pair's first splat record)
+    constexpr bool QUEUE = SCENE_LDS && MTSG_START_QUEUE && (FEAT & MTSG_FEAT_LENS) == 0;
     // a production pass retires the samples whose camera ray misses the scene: without an
     // environment emitter their record is known once the ray exists
     constexpr bool EARLY = QUEUE && MTSG_EARLY_MISS && (FEAT & MTSG_FEAT_ENV) == 0;

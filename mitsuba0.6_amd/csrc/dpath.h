@@ -1170,6 +1170,8 @@ __device__ __forceinline__ f3 xf_point(const float *m, f3 p) {         // transf
     return divs(mk(x, y, z), w);
 }
 
+#include "dsensor.h"   // the sensors' primary rays (the MTSG_FEAT_LENS kernels)
+
 __device__ __forceinline__ f3 area_Le(const MtsgDeviceScene &S, const Hit &h, f3 d) {   // area.cpp:104-109
     const MtsgEmitter &e = S.emitters[S.shapes[h.shape].emitter];
     if (dot(h.sh.n, d) <= 0) return mk(0, 0, 0);
@@ -1256,13 +1258,17 @@ struct PathState {
 // What a path needs to begin (PathShader::produce -> load): the sample's sequence
 // index (or stream key), film position, camera ray direction and 1 / dl.z (the ray's
 // interval is near_clip * invZ .. far_clip * invZ, re-formed by load), its compact
-// pixel and its sample of the chunk; dim: the sampler dimensions produce() consumed
+// pixel and its sample of the chunk; dim: the sampler dimensions produce() consumed.
+// The MTSG_FEAT_LENS kernels (dsensor.h) carry the ray's own origin and interval instead of
+// invZ; no other kernel reads or writes those members
 struct StartRec {
     uint64_t sobolIndex;
     float sx, sy;
     f3 rd;
     float invZ;
     uint32_t pix, jj, dim;
+    f3 ro;
+    float mint, maxt;
 };
 
 // The tiny-scene megakernel's start queue (dmega.h): per wave one batch of up to 64
@@ -1430,6 +1436,10 @@ struct PathShader {
     // feature set is compiled with ENV, which such a scene need not have: have_env() asks the scene
     // there and is the constant `true` in every other kernel
     static constexpr bool DELTA = (FEAT & MTSG_FEAT_DELTA) != 0;
+    // LENS (MTSG_FEAT_LENS): the sensor is thinlens, orthographic or telecentric (dsensor.h): a
+    // primary ray has its own origin and interval (StartRec::ro, mint, maxt), and produce()
+    // draws the aperture sample where the sensor takes one
+    static constexpr bool LENS = (FEAT & MTSG_FEAT_LENS) != 0;
     __device__ __forceinline__ bool have_env() const {
         if constexpr (DELTA) return L.scene.env_emitter >= 0;
         else return true;
@@ -1492,6 +1502,15 @@ struct PathShader {
         r.pix = pix;
         r.sx = (float)px + u;
         r.sy = (float)py + v;
+        if constexpr (LENS) {
+            // renderBlock's aperture draw (integrator.cpp:171-172), then the sensor's ray
+            float ax = 0.5f, ay = 0.5f;
+            if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ax, ay);
+            r.dim = smp.dim;
+            r.invZ = 1.0f;
+            sensor_ray(S.cam, L.cam_lens, r.sx, r.sy, ax, ay, r.ro, r.rd, r.mint, r.maxt);
+            return;
+        }
         // PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298)
         const MtsgCamera &cam = S.cam;
         const f3 nearP = xf_point(cam.sample_to_camera, mk(r.sx * cam.inv_res_x, r.sy * cam.inv_res_y, 0.0f));
@@ -1523,9 +1542,15 @@ struct PathShader {
         st.sx = r.sx;
         st.sy = r.sy;
         st.rd = r.rd;
+        if constexpr (LENS) {
+            st.rmint = r.mint;
+            st.rmaxt = r.maxt;
+            P.its.p = r.ro;           // the ray's own origin
+        } else {
         st.rmint = cam.near_clip * r.invZ;
         st.rmaxt = cam.far_clip * r.invZ;
         P.its.p = cam_origin();   // the ray's origin
+        }
         // Li() prologue (path.cpp:119-133)
         P.L = mk(0, 0, 0);
         P.thr = mk(1.0f, 1.0f, 1.0f);
@@ -1643,15 +1668,25 @@ struct PathShader {
                 // differentials (path.cpp:136-142, perspective.cpp:271-298, integrator.cpp:181)
                 if (ENV && have_env() && P.emitted && (!L.hide_emitters || P.scattered)) {
                     const MtsgCamera &cam = S.cam;
+                    f3 rxd, ryd;
+                    if constexpr (LENS) {
+                        // the sensor's own differentials (dsensor.h).  The aperture sample is not
+                        // kept across the bounce: dimensions 2, 3 of the sample's index, drawn again
+                        // (the same table words as produce()'s next2d: the same bits)
+                        float ax = 0.5f, ay = 0.5f;
+                        if (sensor_needs_aperture(L.cam_lens)) sobol_sample2(SC, smp.sobolIndex, 2, ax, ay);
+                        sensor_ray_diff(cam, L.cam_lens, sx, sy, ax, ay, rd, L.diff_scale, rxd, ryd);
+                    } else {
                     const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
                     const f3 rxl = normalize(add(nearP, ld3(cam.dx))), ryl = normalize(add(nearP, ld3(cam.dy)));
                     const float *W = cam.to_world;
-                    f3 rxd = mk(W[0] * rxl.x + W[1] * rxl.y + W[2] * rxl.z, W[4] * rxl.x + W[5] * rxl.y + W[6] * rxl.z,
-                                W[8] * rxl.x + W[9] * rxl.y + W[10] * rxl.z);
-                    f3 ryd = mk(W[0] * ryl.x + W[1] * ryl.y + W[2] * ryl.z, W[4] * ryl.x + W[5] * ryl.y + W[6] * ryl.z,
-                                W[8] * ryl.x + W[9] * ryl.y + W[10] * ryl.z);
+                    rxd = mk(W[0] * rxl.x + W[1] * rxl.y + W[2] * rxl.z, W[4] * rxl.x + W[5] * rxl.y + W[6] * rxl.z,
+                             W[8] * rxl.x + W[9] * rxl.y + W[10] * rxl.z);
+                    ryd = mk(W[0] * ryl.x + W[1] * ryl.y + W[2] * ryl.z, W[4] * ryl.x + W[5] * ryl.y + W[6] * ryl.z,
+                             W[8] * ryl.x + W[9] * ryl.y + W[10] * ryl.z);
                     rxd = add(rd, mul(sub(rxd, rd), L.diff_scale));   // RayDifferential::scaleDifferential (ray.h:163-168)
                     ryd = add(rd, mul(sub(ryd, rd), L.diff_scale));
+                    }
                     glb_env *E = (glb_env *)S.env;
                     if (REFN && E->constant) {   // ConstantBackgroundEmitter::evalEnvironment (constant.cpp:241-243)
                         P.L = add(P.L, mulv(P.thr, mk(E->radiance[0], E->radiance[1], E->radiance[2])));

@@ -91,7 +91,14 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
         const float sx = (float)px + u, sy = (float)py + v;
         f3 ro, rd;
         float rmint, rmaxt;
-        field_camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
+        if constexpr ((FEAT & MTSG_FEAT_LENS) != 0) {
+            // the other sensors (dsensor.h): the aperture draw of renderBlock, then the sensor's ray
+            float ax = 0.5f, ay = 0.5f;
+            if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ax, ay);
+            sensor_ray(S.cam, L.cam_lens, sx, sy, ax, ay, ro, rd, rmint, rmaxt);
+        } else {
+            field_camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
+        }
 
         // rRec.rayIntersect(sensorRay): the one closest-hit query of the sample
         float mint, maxt;
@@ -164,6 +171,8 @@ extern "C" uint32_t mtsg_launch_bytes_field_kernel() { return (uint32_t)sizeof(M
 typedef void (*FieldKernelFn)(MtsgLaunch, MtsgFieldArgs);
 static FieldKernelFn field_pick(const MtsgLaunch &L) {
     constexpr int EXT = MTSG_FEAT_EXT, ANA = MTSG_FEAT_EXT | MTSG_FEAT_ANA;
+    // thinlens / orthographic / telecentric: one instantiation that holds the analytic shapes too
+    if (L.lens) return L.scene_lds ? field_kernel<true, ANA | MTSG_FEAT_LENS> : field_kernel<false, ANA | MTSG_FEAT_LENS>;
     if (L.ana) return L.scene_lds ? field_kernel<true, ANA> : field_kernel<false, ANA>;
     return L.scene_lds ? field_kernel<true, EXT> : field_kernel<false, EXT>;
 }

@@ -119,8 +119,13 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        // the scene has point / spot / directional emitters (ddelta.h).  Such scenes run one feature
        // set of their own, ENV | EXT | ANA | DELTA, whatever else they hold: its kernels test at
        // run time whether there is an environment (every other set's kernels know)
-       MTSG_FEAT_DELTA = 1024 };
+       MTSG_FEAT_DELTA = 1024,
+       // the sensor is not `perspective` (dsensor.h): primary rays have their own origin, and maybe
+       // an aperture draw.  Such scenes run one feature set of their own that holds everything,
+       // ENV | EXT | ANA | DELTA | LENS; the sensor type is a run-time field (MtsgCameraLens) there
+       MTSG_FEAT_LENS = 2048 };
 #define MTSG_FEAT_SET_DELTA (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA | MTSG_FEAT_DELTA)   // = 1031
+#define MTSG_FEAT_SET_LENS (MTSG_FEAT_SET_DELTA | MTSG_FEAT_LENS)                               // = 3079
 enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_DIRECT = 1, MTSG_INTEGRATOR_VOLPATH = 2 };   // = MTSGPU_INTEGRATOR_*
 enum { MTSG_SAMPLER_SOBOL = 0, MTSG_SAMPLER_INDEPENDENT = 1, MTSG_SAMPLER_SFMT_REPLAY = 2,
        MTSG_SAMPLER_SFMT_BLOCKS = 3 };    // = MTSGPU_SAMPLER_*
@@ -175,6 +180,19 @@ struct MtsgCamera {
     float inv_res_x, inv_res_y, near_clip, far_clip;
     float dx[3], dy[3];
 };
+// What the other projective sensors add to the camera (dsensor.h; read by the
+// MTSG_FEAT_SET_LENS kernels only).  It rides at the end of the launch record, MtsgLaunch::
+// cam_lens, not inside MtsgCamera: every member the perspective kernels read keeps its
+// kernarg offset, so their code is what it was
+struct MtsgCameraLens {
+    int32_t type;             // MTSGPU_SENSOR_*
+    float aperture_radius;    // thinlens: m_apertureRadius; telecentric: m_apertureRadius / m_scale.x
+    float focus_distance;     // thinlens: m_focusDistance; telecentric: m_focusDistance / m_scale.z
+    float ortho_dir[3];       // orthographic: normalize(trafo(Vector(0, 0, 1))), every ray's direction
+    float pad[2];
+};
+enum { MTSG_SENSOR_PERSPECTIVE = 0, MTSG_SENSOR_THINLENS = 1, MTSG_SENSOR_ORTHOGRAPHIC = 2,
+       MTSG_SENSOR_TELECENTRIC = 3 };   // = MTSGPU_SENSOR_*
 
 struct MtsgFilter {
     float radius, scale;
@@ -372,6 +390,9 @@ struct MtsgLaunch {
     uint32_t one_emitter;                  // the emitter CDF is {0.0f, 1.0f} bit for bit: emitter 0 with pdf 1
     const float *face_n;                   // 3 per primitive: unit face normals, staged in LDS with a small scene
                                            // (HitSrc<true>::fn; scene_build.cpp mtsg_face_normal)
+    uint32_t lens;                         // kernel variant: the sensor is not `perspective` (the MTSG_FEAT_SET_LENS
+                                           // kernels; host side only, like `delta`)
+    MtsgCameraLens cam_lens;               // the camera's sensor type, aperture and focus plane (those kernels only)
 };
 
 // The field pass (field_kernel.hip; FieldIntegrator::Li, integrators/misc/field.cpp:124-177):

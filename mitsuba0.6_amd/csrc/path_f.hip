@@ -11,6 +11,8 @@
 // The set kernels are compiled without strictNormals (MTSG_FEAT_NOSTRICT).
 // PATH_FEAT 1031 (MTSG_FEAT_SET_DELTA) is the set of scenes with point / spot /
 // directional emitters: the generic kernel alone, with and without SCENE_LDS.
+// PATH_FEAT 3079 (MTSG_FEAT_SET_LENS) is the set of scenes whose sensor is thinlens,
+// orthographic or telecentric (dsensor.h): the generic kernel alone as well.
 #include "dmega.h"
 
 #define PF_NAME2(a, N) a##N
@@ -50,7 +52,7 @@ PathKernelFn pick_v(const MtsgLaunch &L, bool instr) {
 // (path_kernel.hip path_pick); bits: spec_bits
 PathKernelFn PF_NAME(mtsg_path_pick_f, PATH_FEAT)(const MtsgLaunch &L, int bits, bool instr) {
     switch (bits) {
-#if !(PATH_FEAT & 1024)   // MTSG_FEAT_DELTA: delta-emitter scenes run the generic kernel only (spec_bits gives 0)
+#if !(PATH_FEAT & 1024)   // MTSG_FEAT_DELTA (the delta-emitter and the lens set): the generic kernel only (spec_bits gives 0)
         case 1: return pick_v<spec_feat(1)>(L, instr);
         case 2: return pick_v<spec_feat(2)>(L, instr);
         case 3: return pick_v<spec_feat(3)>(L, instr);

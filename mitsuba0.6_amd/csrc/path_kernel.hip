@@ -69,6 +69,38 @@ __device__ __forceinline__ f3 env_camera(const MtsgLaunch &L, float sx, float sy
     return env_eval_diff(E, rd, rxd, ryd);
 }
 
+// the same for the sensors of dsensor.h (the MTSG_FEAT_LENS kernels): their own differentials
+__device__ __forceinline__ f3 env_sensor(const MtsgLaunch &L, float sx, float sy, float ax, float ay, f3 rd) {
+    glb_env *E = (glb_env *)L.scene.env;
+    if (E->constant) return mk(E->radiance[0], E->radiance[1], E->radiance[2]);
+    f3 rxd, ryd;
+    sensor_ray_diff(L.scene.cam, L.cam_lens, sx, sy, ax, ay, rd, L.diff_scale, rxd, ryd);
+    return env_eval_diff(E, rd, rxd, ryd);
+}
+
+// direct_kernel's primary ray and its camera-miss lookup per feature set: the pinhole's
+// camera_ray / env_camera as they were, or (MTSG_FEAT_LENS) the aperture draw of renderBlock
+// (integrator.cpp:171-172, before Li), the sensor's ray and its own differentials
+template <bool LENS> struct DirectAperture {};
+template <> struct DirectAperture<true> { float x, y; };
+template <bool LENS>
+__device__ __forceinline__ void direct_primary(const MtsgLaunch &L, const SobolCtx &SC, SamplerState &smp, int px, int py,
+                                               float sx, float sy, DirectAperture<LENS> &ap, f3 &ro, f3 &rd, float &mint,
+                                               float &maxt) {
+    if constexpr (LENS) {
+        ap.x = ap.y = 0.5f;
+        if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ap.x, ap.y);
+        sensor_ray(L.scene.cam, L.cam_lens, sx, sy, ap.x, ap.y, ro, rd, mint, maxt);
+    } else {
+        camera_ray(L.scene.cam, sx, sy, ro, rd, mint, maxt);
+    }
+}
+template <bool LENS>
+__device__ __forceinline__ f3 direct_env_miss(const MtsgLaunch &L, float sx, float sy, const DirectAperture<LENS> &ap, f3 rd) {
+    if constexpr (LENS) return env_sensor(L, sx, sy, ap.x, ap.y, rd);
+    else return env_camera(L, sx, sy, rd);
+}
+
 // Scene::sampleEmitterDirect without the visibility test (scene.cpp:828-852):
 // value = radiance / (pdf * emPdf) and pdf = dRec.pdf * emPdf when pdf != 0
 // delta: the sample is a delta emitter's (ddelta.h; Emitter::isOnSurface() false: direct.cpp:235)
@@ -211,7 +243,8 @@ SHADOW_ANY_CALL bool shadow_any(NodeT *nodes, TriT *tris, f3 o, f3 d, float mint
 template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLaunch L) {
     constexpr bool ENV = (FEAT & MTSG_FEAT_ENV) != 0, EXT = (FEAT & MTSG_FEAT_EXT) != 0,
-                   ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0;
+                   ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0,
+                   LENS = (FEAT & MTSG_FEAT_LENS) != 0;   // the sensor's own ray (dsensor.h)
     extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     // the delta-emitter feature set is compiled with ENV; its scenes need not have an environment
@@ -286,13 +319,14 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
         const float sx = (float)px + u, sy = (float)py + v;
         f3 ro, rd;
         float rmint, rmaxt;
-        camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
+        DirectAperture<LENS> ap;
+        direct_primary<LENS>(L, SC, smp, px, py, sx, sy, ap, ro, rd, rmint, rmaxt);
         f3 Li = mk(0, 0, 0);
         Hit its;
         const bool hit = closest(ro, rd, rmint, rmaxt, its);
         const float alpha = L.has_alpha ? (hit ? 1.0f : 0.0f) : 1.0f;
         if (!hit) {
-            if (ENV && haveEnv && !L.hide_emitters) Li = env_camera(L, sx, sy, rd);
+            if (ENV && haveEnv && !L.hide_emitters) Li = direct_env_miss<LENS>(L, sx, sy, ap, rd);
         } else {
             auto &sh = hs.shapes[its.shape];
             GBsdf &bsdf = ((GBsdf *)S.bsdfs)[sh.bsdf];
@@ -700,13 +734,15 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
                                      : 0;
     // the traversal stacks, or in their place the megakernel's start queue (dpath.h mtsg_start_queue)
     size_t tail = ((size_t)L.stack_depth * 3 * BLOCK + 1) / 2;
-    if (mtsg_start_queue(L)) tail = std::max<size_t>(tail, MTSG_QUEUE_WORDS);
+    if (mtsg_path_start_queue(L)) tail = std::max<size_t>(tail, MTSG_QUEUE_WORDS);
     return ((size_t)L.lds_dims * L.nibbles * 16 + MTSG_LUT_WORDS + scene + tail) * 4;
 }
 
-bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L); }
+// (the MTSG_FEAT_LENS kernels are built without the queue: dmega.h QUEUE)
+bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L) && !L.lens; }
 
 int mtsg_path_features(const MtsgLaunch &L) {
+    if (L.lens) return MTSG_FEAT_SET_LENS;     // thinlens / orthographic / telecentric: the one set that holds everything
     if (L.delta) return MTSG_FEAT_SET_DELTA;   // delta-emitter scenes: the one set that holds everything
     return (L.scene.env_emitter >= 0 ? MTSG_FEAT_ENV : 0) | ((L.ext || L.ana) ? MTSG_FEAT_EXT : 0) |
            (L.ana ? MTSG_FEAT_ANA : 0);
@@ -717,7 +753,7 @@ int mtsg_path_features(const MtsgLaunch &L) {
 // (render_plan.cpp plan_render, L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
 // small scenes staged in LDS and the direct integrator take the generic kernel.
 static int spec_bits(const MtsgLaunch &L) {
-    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta) return 0;   // (delta: the generic set only)
+    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta || L.lens) return 0;   // (delta, lens: the generic set only)
     const int b = ((L.bset & MTSG_FEAT_GGX) ? 1 : 0) | ((L.bset & MTSG_FEAT_NORD) ? 2 : 0) | ((L.bset & MTSG_FEAT_NORC) ? 4 : 0);
     return b | ((b && (L.bset & MTSG_FEAT_NOREFN) && (mtsg_path_features(L) & MTSG_FEAT_ENV)) ? 8 : 0);
 }
@@ -733,6 +769,7 @@ static PathKernelFn path_pick(const MtsgLaunch &L, bool instr) {
         case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_path_pick_f3(L, bits, instr);
         case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_pick_f6(L, bits, instr);
         case MTSG_FEAT_SET_DELTA: return mtsg_path_pick_f1031(L, bits, instr);
+        case MTSG_FEAT_SET_LENS: return mtsg_path_pick_f3079(L, bits, instr);
         default: return mtsg_path_pick_f7(L, bits, instr);
     }
 }
@@ -754,6 +791,7 @@ hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool st
             case MTSG_FEAT_ENV | MTSG_FEAT_EXT: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT>(L, grid, stream); break;
             case MTSG_FEAT_EXT | MTSG_FEAT_ANA: launch_direct<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
             case MTSG_FEAT_SET_DELTA: launch_direct<MTSG_FEAT_SET_DELTA>(L, grid, stream); break;
+            case MTSG_FEAT_SET_LENS: launch_direct<MTSG_FEAT_SET_LENS>(L, grid, stream); break;
             default: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
         }
         return hipGetLastError();

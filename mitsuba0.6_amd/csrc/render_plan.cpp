@@ -164,7 +164,8 @@ uint32_t plan_bset(const HostScene &H, const mtsgpu_render_params &P, const Rend
     float extent = 0.0f;
     for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs(H.aabb_min[a]), std::fabs(H.aabb_max[a])));
     // (the set kernels are built without strictNormals: MTSG_FEAT_NOSTRICT)
-    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals || !H.deltas.empty()) ? 0u
+    const bool lens = H.cam_lens.type != MTSG_SENSOR_PERSPECTIVE;   // (the lens set, like the delta set: the generic kernel)
+    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals || !H.deltas.empty() || lens) ? 0u
                     : (ggx ? (uint32_t)MTSG_FEAT_GGX : 0u) | (rc ? 0u : (uint32_t)MTSG_FEAT_NORC) |
                           (rd ? 0u : (uint32_t)MTSG_FEAT_NORD);
     // envmap-only scenes (no area light, no constant emitter): the set kernels without
@@ -188,7 +189,11 @@ void plan_variant(MtsgLaunch &L, const HostScene &H, const mtsgpu_render_params 
     L.ana = H.analytic.empty() ? 0u : 1u;
     // point / spot / directional emitters: the MTSG_FEAT_SET_DELTA kernels, the generic BSDF set only
     L.delta = H.deltas.empty() ? 0u : 1u;
-    L.all_diffuse = (K.no_diff_variant || L.delta) ? 0u : 1u;
+    // thinlens / orthographic / telecentric sensors: the MTSG_FEAT_SET_LENS kernels, the generic BSDF set
+    // only; no start queue (mtsg_path_start_queue) and, compiled with ENV, no early miss
+    L.lens = H.cam_lens.type != MTSG_SENSOR_PERSPECTIVE ? 1u : 0u;
+    L.cam_lens = H.cam_lens;
+    L.all_diffuse = (K.no_diff_variant || L.delta || L.lens) ? 0u : 1u;
     for (const MtsgBsdf &b : H.bsdfs) L.all_diffuse &= b.type == MTSGPU_BSDF_DIFFUSE ? 1u : 0u;
     L.bset = plan_bset(H, P, K);
     // large scenes are latency-bound: run 4 waves/SIMD when 4 blocks' traversal
@@ -304,6 +309,9 @@ int plan_render(const HostScene &H, const mtsgpu_render_params &Pr, uint32_t num
     if (replay && FJ)
         return bad(err, "field pass: the SFMT replay samplers' draw positions depend on how many numbers the "
                         "radiance integrator consumed; a separate pass cannot reproduce the sample positions");
+    if (replay && H.cam_lens.type != MTSG_SENSOR_PERSPECTIVE)
+        return bad(err, "SFMT replay: the perspective sensor only (nothing could check a replayed aperture stream of "
+                        "a thinlens, orthographic or telecentric sensor)");
     if (replay && (!pathLike || L.row_stride > 1 || P->width > 65535 || P->height > 65535))
         return bad(err, "SFMT replay: path/volpath over a whole crop window (no row shards)");
     L.sampler = (uint32_t)P->sampler;
@@ -463,14 +471,18 @@ WfPlan plan_wavefront(const RenderPlan &plan, const HostScene &H, const RenderKn
 // FEAT's low 8 bits | WAVES << 8 | SCENE_LDS << 12 | INSTR << 13 | (FEAT & NOSTRICT) << 14 (the
 // set kernels' strictNormals-free build) | (FEAT & NOREFN) << 15; 1 << 16 for the wavefront engine;
 // 1 << 18 (MTSGPU_VARIANT_DELTA) on top of any of these: the MTSG_FEAT_SET_DELTA instantiations of
-// scenes with delta emitters -- the megakernel, direct_kernel or the wavefront shade kernels
+// scenes with delta emitters -- the megakernel, direct_kernel or the wavefront shade kernels;
+// 1 << 19 (MTSGPU_VARIANT_LENS): the MTSG_FEAT_SET_LENS instantiations of scenes whose sensor is
+// not `perspective` (those kernels hold the delta emitters too: bit 18 is then set only with
+// such emitters in the scene), the field pass's included
 // (tests and A/B logs read it)
 uint64_t plan_variant_word(const RenderPlan &plan) {
     const MtsgLaunch &L = plan.L;
-    const uint64_t dbit = L.delta ? 1ull << 18 : 0;
+    const uint64_t lbit = L.lens ? 1ull << 19 : 0;
+    const uint64_t dbit = (L.delta ? 1ull << 18 : 0) | lbit;
     if (plan.engine == MTSG_ENGINE_WAVEFRONT) return (1ull << 16) | dbit;
     if (plan.engine == MTSG_ENGINE_FIELDS)   // field_kernel<SCENE_LDS, ..>: 1 << 17 | SCENE_LDS << 12
-        return (1ull << 17) | ((uint64_t)L.scene_lds << 12);
+        return (1ull << 17) | ((uint64_t)L.scene_lds << 12) | lbit;
     const int v = mtsg_path_variant(L);
     return dbit | (uint64_t)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) | (plan.instr ? 1 << 13 : 0) |
                       ((v & MTSG_FEAT_NOSTRICT) ? 1 << 14 : 0) | ((v & MTSG_FEAT_NOREFN) ? 1 << 15 : 0));

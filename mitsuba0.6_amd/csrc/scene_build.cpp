@@ -203,8 +203,71 @@ int configure_analytic(const mtsgpu_mesh_desc &m, MtsgAnalytic &a, float lo[3], 
     return MTSGPU_OK;
 }
 
-int configure_camera(const mtsgpu_sensor_desc &s, MtsgCamera &cam, std::string &err) {
+// OrthographicCamera / TelecentricLensCamera ctor + configure() (orthographic.cpp:73-135,
+// telecentric.cpp:74-153, sensor.cpp:156-170): the orthographic sampleToCamera and its
+// dx / dy, the world direction of an orthographic ray, telecentric's aperture radius and
+// focus distance divided by m_scale as sampleRayDifferential uses them
+int configure_ortho_camera(const mtsgpu_sensor_desc &s, MtsgCamera &cam, MtsgCameraLens &ln, std::string &err) {
+    const float aspect = (float)s.film_width / (float)s.film_height;
+    if (!(s.near_clip > 0)) { err = "The 'nearClip' parameter must be greater than zero!"; return MTSGPU_EINVAL; }
+    if (!(s.near_clip < s.far_clip)) { err = "The 'nearClip' parameter must be smaller than 'farClip'."; return MTSGPU_EINVAL; }
+    // Transform::orthographic (transform.cpp:154-157), crop = film
+    Xf ortho = compose(scale(1.0f, 1.0f, 1.0f / (s.far_clip - s.near_clip)), translate(0.0f, 0.0f, -s.near_clip));
+    Xf a = scale(1.0f / 1.0f, 1.0f / 1.0f, 1.0f);
+    Xf b = translate(-0.0f, -0.0f, 0.0f);
+    Xf c = scale(-0.5f, -0.5f * aspect, 1.0f);
+    Xf d = translate(-1.0f, -1.0f / aspect, 0.0f);
+    Xf camToSample = compose(compose(compose(compose(a, b), c), d), ortho);
+    const M4 &s2c = camToSample.inv;
+    M4 W;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            cam.sample_to_camera[i * 4 + j] = s2c.m[i][j];
+            cam.to_world[i * 4 + j] = W.m[i][j] = s.to_world[i * 4 + j];
+        }
+    cam.inv_res_x = (float)1 / (float)s.film_width;
+    cam.inv_res_y = (float)1 / (float)s.film_height;
+    cam.near_clip = s.near_clip;
+    cam.far_clip = s.far_clip;
+    V o0 = xf_point(s2c, v(0.0f, 0.0f, 0.0f));
+    V dx = xf_point(s2c, v(cam.inv_res_x, 0.0f, 0.0f)) - o0;
+    V dy = xf_point(s2c, v(0.0f, cam.inv_res_y, 0.0f)) - o0;
+    put3(cam.dx, dx);
+    put3(cam.dy, dy);
+    put3(ln.ortho_dir, normalize(xf_vec(W, v(0.0f, 0.0f, 1.0f))));
+    if (s.type == MTSGPU_SENSOR_TELECENTRIC) {
+        const float scaleX = length(xf_vec(W, v(1.0f, 0.0f, 0.0f))), scaleZ = length(xf_vec(W, v(0.0f, 0.0f, 1.0f)));
+        ln.aperture_radius = s.aperture_radius / scaleX;
+        ln.focus_distance = s.focus_distance / scaleZ;
+    }
+    return MTSGPU_OK;
+}
+
+int configure_camera(const mtsgpu_sensor_desc &s, MtsgCamera &cam, MtsgCameraLens &ln, std::string &err) {
     if (s.film_width == 0 || s.film_height == 0) { err = "film size must be positive"; return MTSGPU_EINVAL; }
+    std::memset(&cam, 0, sizeof cam);
+    std::memset(&ln, 0, sizeof ln);
+    if (s.type < MTSGPU_SENSOR_PERSPECTIVE || s.type > MTSGPU_SENSOR_TELECENTRIC) {
+        err = "unknown sensor type (perspective, thinlens, orthographic, telecentric)"; return MTSGPU_EINVAL;
+    }
+    ln.type = s.type;
+    if (s.type == MTSGPU_SENSOR_ORTHOGRAPHIC || s.type == MTSGPU_SENSOR_TELECENTRIC)
+        return configure_ortho_camera(s, cam, ln, err);
+    if (s.type == MTSGPU_SENSOR_THINLENS) {
+        // ThinLens ctor (thinlens.cpp:124-143); sampleToCamera, dx and dy are perspective's (:156-193)
+        ln.aperture_radius = s.aperture_radius == 0 ? 1e-4f : s.aperture_radius;   // Epsilon
+        ln.focus_distance = s.focus_distance;
+        // Transform::hasScale (transform.h:76-90)
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j) {
+                float sum = 0;
+                for (int k = 0; k < 3; ++k) sum += s.to_world[4 * i + k] * s.to_world[4 * j + k];
+                if (i == j ? std::fabs(sum - 1) > 1e-3f : std::fabs(sum) > 1e-3f) {
+                    err = "Scale factors in the camera-to-world transformation are not allowed!";
+                    return MTSGPU_EINVAL;
+                }
+            }
+    }
     const float aspect = (float)s.film_width / (float)s.film_height;
     float xfov = s.fov;
     int axis = s.fov_axis;
@@ -1040,12 +1103,34 @@ int build_envmap(const mtsgpu_emitter_desc &e, int index, HostScene &S, std::str
 void envmap_bsphere(HostScene &S, const mtsgpu_sensor_desc &sensor) {
     M4 C;
     for (int i = 0; i < 16; ++i) C.m[i / 4][i % 4] = sensor.to_world[i];
-    const V cp = xf_point(C, v(0.0f, 0.0f, 0.0f));   // AnimatedTransform::getTranslationBounds (track.cpp:79-83)
     float mn[3], mx[3];
-    const float p[3] = {cp.x, cp.y, cp.z};
-    for (int a = 0; a < 3; ++a) {
-        mn[a] = fmin_std(S.aabb_min[a], p[a]);
-        mx[a] = fmax_std(S.aabb_max[a], p[a]);
+    for (int a = 0; a < 3; ++a) { mn[a] = S.aabb_min[a]; mx[a] = S.aabb_max[a]; }
+    auto grow = [&](V q) {
+        const float p[3] = {q.x, q.y, q.z};
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = fmin_std(mn[a], p[a]);
+            mx[a] = fmax_std(mx[a], p[a]);
+        }
+    };
+    if (S.cam_lens.type == MTSGPU_SENSOR_PERSPECTIVE) {
+        grow(xf_point(C, v(0.0f, 0.0f, 0.0f)));   // AnimatedTransform::getTranslationBounds (track.cpp:79-83)
+    } else {
+        // the sensor's own getAABB(): the aperture's box (thinlens.cpp:516-520) or the film rectangle
+        // sampleToCamera((0,0,0)) .. sampleToCamera((1,1,0)) (orthographic.cpp:296-302,
+        // telecentric.cpp:437-443), its 8 corners through toWorld (getSpatialBounds, track.cpp:123-129)
+        float lo[3], hi[3];
+        if (S.cam_lens.type == MTSGPU_SENSOR_THINLENS) {
+            const float r = S.cam_lens.aperture_radius;
+            lo[0] = -r; lo[1] = -r; lo[2] = 0.0f; hi[0] = r; hi[1] = r; hi[2] = 0.0f;
+        } else {
+            M4 s2c;
+            for (int i = 0; i < 16; ++i) s2c.m[i / 4][i % 4] = S.cam.sample_to_camera[i];
+            const V a = xf_point(s2c, v(0.0f, 0.0f, 0.0f)), b = xf_point(s2c, v(1.0f, 1.0f, 0.0f));
+            lo[0] = fmin_std(a.x, b.x); lo[1] = fmin_std(a.y, b.y); lo[2] = fmin_std(a.z, b.z);
+            hi[0] = fmax_std(a.x, b.x); hi[1] = fmax_std(a.y, b.y); hi[2] = fmax_std(a.z, b.z);
+        }
+        for (int j = 0; j < 8; ++j)   // AABB::getCorner: bit 0 -> x, bit 1 -> y, bit 2 -> z
+            grow(xf_point(C, v((j & 1) ? hi[0] : lo[0], (j & 2) ? hi[1] : lo[1], (j & 4) ? hi[2] : lo[2])));
     }
     const V center = v((mx[0] + mn[0]) * 0.5f, (mx[1] + mn[1]) * 0.5f, (mx[2] + mn[2]) * 0.5f);
     const float radius = length(center - v(mx[0], mx[1], mx[2]));
@@ -1248,7 +1333,7 @@ int mtsg_configure_scene(const mtsgpu_scene_desc *D, HostScene &S, std::string &
     S = HostScene();
     std::memset(&S.env, 0, sizeof S.env);
     S.env.emitter = -1;
-    int rc = configure_camera(D->sensor, S.cam, err);
+    int rc = configure_camera(D->sensor, S.cam, S.cam_lens, err);
     if (rc) return rc;
     S.film_w = D->sensor.film_width;
     S.film_h = D->sensor.film_height;

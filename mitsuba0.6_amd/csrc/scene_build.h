@@ -41,6 +41,7 @@ struct HostScene {
     float em_norm = 0;
     float aabb_min[3], aabb_max[3];
     MtsgCamera cam;
+    MtsgCameraLens cam_lens;   // sensor type, aperture, focus plane (MtsgLaunch::cam_lens)
     uint32_t film_w = 0, film_h = 0;
     uint32_t bvh_depth = 0;
     // environment emitter (env.emitter < 0: none); pointers in `env` are set at upload

@@ -248,6 +248,8 @@ def lookup_host(m, scramble, px_py_j):
 PLAN_ENGINES = ('megakernel', 'wavefront', 'fields')
 # debug counter 15: the delta-emitter instantiations ran (MTSG_FEAT_DELTA; megakernel, direct or wavefront)
 VARIANT_DELTA = 1 << 18
+# ... and the instantiations of scenes whose sensor is not `perspective` (MTSG_FEAT_SET_LENS, the field pass's too)
+VARIANT_LENS = 1 << 19
 
 
 def kernel_variant_of(word):
@@ -258,10 +260,11 @@ def kernel_variant_of(word):
     if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
         return None
     feat = ((c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0) |
-            (1024 if c & VARIANT_DELTA else 0))
+            (1024 if c & (VARIANT_DELTA | VARIANT_LENS) else 0) | (2048 if c & VARIANT_LENS else 0))
     instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
     b = lambda v: 'true' if v else 'false'
     return {'instr': instr, 'scene_lds': lds, 'feat': feat, 'waves': waves, 'delta': bool(c & VARIANT_DELTA),
+            'lens': bool(c & VARIANT_LENS),
             'name': 'path_kernel<%s, %s, %d, %d>' % (b(instr), b(lds), feat, waves)}
 
 

@@ -275,6 +275,31 @@ class Sensor:
     toWorld: np.ndarray = field(default_factory=lambda: np.eye(4, dtype=np.float32))
     width: int = 768
     height: int = 576
+    # 'perspective' | 'thinlens' | 'orthographic' | 'telecentric' (src/sensors); fov and
+    # fovAxis belong to the first two.  shutterOpen == shutterClose: no time sample
+    type: str = 'perspective'
+    apertureRadius: Optional[float] = None   # thinlens: required (0 becomes Epsilon); telecentric: 0
+    focusDistance: Optional[float] = None    # thinlens, telecentric: farClip (sensor.cpp:162)
+
+    TYPES = ('perspective', 'thinlens', 'orthographic', 'telecentric')
+
+    def __post_init__(self):
+        if self.type not in self.TYPES:
+            raise ValueError('sensor type "%s" (%s)' % (self.type, ', '.join(self.TYPES)))
+        lens = self.type in ('thinlens', 'telecentric')
+        if not lens and (self.apertureRadius is not None or self.focusDistance is not None):
+            raise ValueError("sensor '%s' has no 'apertureRadius' / 'focusDistance'" % self.type)
+        if self.type == 'thinlens':                                      # thinlens.cpp:131-142
+            if self.apertureRadius is None:
+                raise ValueError('Property "apertureRadius" has not been specified!')
+            if self.apertureRadius == 0:
+                self.apertureRadius = 1e-4                               # Epsilon
+            if transform_has_scale(Transform(np.asarray(self.toWorld, np.float32).reshape(4, 4))):
+                raise ValueError('Scale factors in the camera-to-world transformation are not allowed!')
+        if self.type == 'telecentric' and self.apertureRadius is None:   # telecentric.cpp:81
+            self.apertureRadius = 0.0
+        if lens and self.focusDistance is None:
+            self.focusDistance = self.farClip
 
 
 def look_at(origin, target, up):
@@ -392,6 +417,10 @@ class Scene:
         d.sensor.near_clip, d.sensor.far_clip = s.nearClip, s.farClip
         d.sensor.to_world[:] = [float(x) for x in np.asarray(s.toWorld, np.float32).reshape(-1)]
         d.sensor.film_width, d.sensor.film_height = s.width, s.height
+        d.sensor.type = {'perspective': abi.SENSOR_PERSPECTIVE, 'thinlens': abi.SENSOR_THINLENS,
+                         'orthographic': abi.SENSOR_ORTHOGRAPHIC, 'telecentric': abi.SENSOR_TELECENTRIC}[s.type]
+        d.sensor.aperture_radius = s.apertureRadius or 0.0
+        d.sensor.focus_distance = s.focusDistance or 0.0
         d._keep = (keep, md, bd, ed)
         return d
 

@@ -17,7 +17,11 @@ Plugins:
   `direct` (shadingSamples, emitterSamples, bsdfSamples, strictNormals,
   hideEmitters); `multichannel` with nested `field` (field, undefined) and at
   most one of `path` / `volpath` / `direct`.
-- sensor `perspective` (fov/fovAxis or focalLength, near/farClip, toWorld),
+- sensors `perspective` and `thinlens` (fov/fovAxis or focalLength, near/farClip, toWorld;
+  thinlens: apertureRadius, focusDistance), `orthographic` and `telecentric` (near/farClip,
+  toWorld, which may carry scale; telecentric: apertureRadius, focusDistance); no motion
+  blur (shutterOpen == shutterClose, no `<animation>`); `spherical` and the meter sensors
+  are not implemented;
   with sampler `sobol` (sampleCount, scramble) or `independent` (sampleCount;
   the default without a <sampler>), film `hdrfilm`, `mfilm` or `ldrfilm` (size,
   crop window, pixel/file formats; ldrfilm's tonemapMethod, gamma, exposure, key
@@ -530,8 +534,11 @@ class XMLSceneLoader:
     def _sensor(self, p, integ):
         if p is None:
             raise SceneError('no <sensor>')
-        if p.plugin != 'perspective':
-            raise NotImplementedError('sensor "%s" (only "perspective")' % p.plugin)
+        if p.plugin not in Sensor.TYPES:
+            raise NotImplementedError('sensor "%s" (perspective, thinlens, orthographic, telecentric)' % p.plugin)
+        if p.plugin != 'perspective' and float(p.get('shutterOpen', 0.0)) != float(p.get('shutterClose', 0.0)):
+            raise NotImplementedError('sensor "%s": shutterOpen != shutterClose (no time sample, no motion blur)'
+                                      % p.plugin)
         film = next((c for _, c in p.children if c.tag == 'film'), None)
         sampler = next((c for _, c in p.children if c.tag == 'sampler'), None)
         width, height = 768, 576
@@ -584,9 +591,12 @@ class XMLSceneLoader:
         if sampler is not None:
             spp = sampler.get('sampleCount', 4)
             scramble = sampler.get('scramble', 0) if kind == 'sobol' else 0
+        ortho = p.plugin in ('orthographic', 'telecentric')
         if 'fov' in p and 'focalLength' in p:
             raise SceneError("Please specify either a focal length ('focalLength') or a field of view ('fov')!")
-        if 'fov' in p:
+        if ortho:                      # no fov (orthographic.cpp, telecentric.cpp: ProjectiveCamera alone)
+            fov, axis = Sensor.fov, 'x'
+        elif 'fov' in p:
             fov, axis = float(p['fov']), p.get('fovAxis', 'x').lower()
         else:
             f = p.get('focalLength', '50mm')
@@ -603,8 +613,15 @@ class XMLSceneLoader:
             fov = float(f32(f32(f32(360) / f32(math.pi)) * f32(libm.atanf(float(arg)))))
             axis = 'diagonal'
         tw = p.get('toWorld', Transform())
-        sensor = Sensor(fov=fov, fovAxis=axis, nearClip=float(p.get('nearClip', 1e-2)),
-                        farClip=float(p.get('farClip', 1e4)), toWorld=tw.m, width=width, height=height)
+        lens = {}
+        if p.plugin in ('thinlens', 'telecentric'):
+            lens = {k: float(p[k]) for k in ('apertureRadius', 'focusDistance') if k in p}
+        try:
+            sensor = Sensor(fov=fov, fovAxis=axis, nearClip=float(p.get('nearClip', 1e-2)),
+                            farClip=float(p.get('farClip', 1e4)), toWorld=tw.m, width=width, height=height,
+                            type=p.plugin, **lens)
+        except ValueError as e:
+            raise SceneError(str(e))
         integ.sampleCount, integ.scramble, integ.sampler = spp, scramble, kind
         integ.rfilter, integ.rfilterParam, integ.hasAlpha = rfilter, rparam, has_alpha
         integ.crop = crop
@@ -772,9 +789,13 @@ def save_scene(scene, integ, directory, name='scene.xml'):
     L = ['<?xml version="1.0" encoding="utf-8"?>', '<scene version="0.6.0">']
     L += _integrator_xml(integ, '  ')
     s = scene.sensor
-    L.append('  <sensor type="perspective">')
-    L.append('    <float name="fov" value="%s"/>' % _fmt(s.fov))
-    L.append('    <string name="fovAxis" value="%s"/>' % s.fovAxis)
+    L.append('  <sensor type="%s">' % s.type)
+    if s.type in ('perspective', 'thinlens'):
+        L.append('    <float name="fov" value="%s"/>' % _fmt(s.fov))
+        L.append('    <string name="fovAxis" value="%s"/>' % s.fovAxis)
+    if s.type in ('thinlens', 'telecentric'):
+        L.append('    <float name="apertureRadius" value="%s"/>' % _fmt(s.apertureRadius))
+        L.append('    <float name="focusDistance" value="%s"/>' % _fmt(s.focusDistance))
     L.append('    <float name="nearClip" value="%s"/>' % _fmt(s.nearClip))
     L.append('    <float name="farClip" value="%s"/>' % _fmt(s.farClip))
     L.append('    <transform name="toWorld">%s</transform>' % _matrix(s.toWorld))
