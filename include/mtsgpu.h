@@ -632,6 +632,18 @@ int mtsgpu_debug_sfmt(mtsgpu_ctx *ctx, uint64_t seed, int clone, uint64_t *out, 
  * halves); rows h0+1, cols h0*(w0+1), weights h0 floats (any may be NULL). */
 int mtsgpu_debug_env_tables(const mtsgpu_scene_desc *scene, float *params, uint16_t *texels, size_t texel_cap,
                             float *rows, float *cols, float *weights);
+/* Host-only (no device needed): configure `scene` and write one 64-bit FNV-1a hash per
+ * member of the configured scene (csrc/scene_build.h HostScene), in declaration order:
+ * nodes hnodes tris prim_vtx dpdu positions normals face_n shapes bsdfs emitters deltas
+ * area_cdf em_cdf em_norm aabb_min aabb_max cam cam_lens film_w film_h bvh_depth env
+ * env_texels env_cdf_rows env_cdf_cols env_row_weights env_guide_rows env_guide_cols rtrans
+ * texcoords ext analytic.  A vector's hash is of its elements' bytes; `env` is the record
+ * up to its first pointer plus the two guide bit counts; `ext` is one byte.  qnodes and
+ * launch, which configure does not fill, are left out.  *n receives the number of hashes
+ * (also when cap is too small, which is MTSGPU_EINVAL); on a configure error its code is
+ * returned and its text copied to msg.  (tests/test_scene_digest_host.py) */
+int mtsgpu_scene_digest_host(const mtsgpu_scene_desc *scene, uint64_t *out, size_t cap, uint32_t *n, char *msg,
+                             size_t msg_cap);
 /* ---- device groups: one render over several GPUs ------------------------
  * SURVEY.md 8(b)'s `mtsgpu_create(const int *devices, int n, ...)`: a group
  * holds one context per listed device (a device may be listed twice: two

@@ -1001,7 +1001,7 @@ int mtsgpu_scan_host(const mtsgpu_scene_desc *scene, float *records, size_t cap,
     return MTSGPU_OK;
 }
 
-// the per-primitive unit face normals upload_scene forms for LDS scenes (scene_build.cpp
+// the per-primitive unit face normals upload_scene forms for LDS scenes (configure_shape.cpp
 // mtsg_face_normal), with the vertex positions they were formed from (9 floats per primitive)
 int mtsgpu_face_normals_host(const mtsgpu_scene_desc *scene, float *normals, float *corners, size_t prim_cap,
                              uint32_t *num_prims) {
@@ -1265,6 +1265,44 @@ int mtsgpu_debug_env_tables(const mtsgpu_scene_desc *scene, float *params, uint1
     if (rows) std::memcpy(rows, H.env_cdf_rows.data(), H.env_cdf_rows.size() * sizeof(float));
     if (cols) std::memcpy(cols, H.env_cdf_cols.data(), H.env_cdf_cols.size() * sizeof(float));
     if (weights) std::memcpy(weights, H.env_row_weights.data(), H.env_row_weights.size() * sizeof(float));
+    return MTSGPU_OK;
+}
+
+// diagnostics: one hash per member of the configured scene (tests/test_scene_digest_host.py)
+static uint64_t fnv1a(const void *p, size_t bytes, uint64_t h = 0xcbf29ce484222325ull) {
+    const unsigned char *b = (const unsigned char *)p;
+    for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    return h;
+}
+
+int mtsgpu_scene_digest_host(const mtsgpu_scene_desc *scene, uint64_t *out, size_t cap, uint32_t *n, char *msg,
+                             size_t msg_cap) {
+    if (!scene || !n) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    const int rc = mtsg_configure_scene(scene, H, err);
+    if (msg && msg_cap) {
+        std::strncpy(msg, err.c_str(), msg_cap - 1);
+        msg[msg_cap - 1] = 0;
+    }
+    if (rc) return rc;
+    auto vec = [](const auto &v) { return fnv1a(v.data(), v.size() * sizeof(v[0])); };
+    const unsigned char ext = H.ext ? 1 : 0;
+    uint64_t env = fnv1a(&H.env, offsetof(MtsgEnv, texels));
+    env = fnv1a(&H.env.guide_rbits, sizeof H.env.guide_rbits, env);
+    env = fnv1a(&H.env.guide_cbits, sizeof H.env.guide_cbits, env);
+    const uint64_t d[] = {
+        vec(H.nodes), vec(H.hnodes), vec(H.tris), vec(H.prim_vtx), vec(H.dpdu), vec(H.positions),
+        vec(H.normals), vec(H.face_n), vec(H.shapes), vec(H.bsdfs), vec(H.emitters), vec(H.deltas),
+        vec(H.area_cdf), vec(H.em_cdf), fnv1a(&H.em_norm, sizeof H.em_norm),
+        fnv1a(H.aabb_min, sizeof H.aabb_min), fnv1a(H.aabb_max, sizeof H.aabb_max), fnv1a(&H.cam, sizeof H.cam),
+        fnv1a(&H.cam_lens, sizeof H.cam_lens), fnv1a(&H.film_w, sizeof H.film_w), fnv1a(&H.film_h, sizeof H.film_h),
+        fnv1a(&H.bvh_depth, sizeof H.bvh_depth), env, vec(H.env_texels), vec(H.env_cdf_rows),
+        vec(H.env_cdf_cols), vec(H.env_row_weights), vec(H.env_guide_rows), vec(H.env_guide_cols),
+        vec(H.rtrans), vec(H.texcoords), fnv1a(&ext, 1), vec(H.analytic)};
+    *n = (uint32_t)(sizeof d / sizeof d[0]);
+    if (!out || cap < *n) return MTSGPU_EINVAL;
+    std::memcpy(out, d, sizeof d);
     return MTSGPU_OK;
 }
 

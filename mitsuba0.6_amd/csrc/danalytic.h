@@ -10,7 +10,7 @@
 //                  Sphere::sampleDirect/pdfDirect (sphere.cpp:286-387)
 //
 // Per-shape constants (transforms, frame, 1/area) come from the host
-// (scene_build.cpp:configure_analytic) in an MtsgAnalytic record.
+// (configure_shape.cpp:configure_analytic) in an MtsgAnalytic record.
 #pragma once
 #include "dmath.h"
 #include "layout.h"

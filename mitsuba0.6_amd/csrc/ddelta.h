@@ -9,7 +9,7 @@
 // them, so they have no pdfDirect partner and no emitted-radiance term; the
 // integrators weight their estimate with bsdfPdf = 0 (path.cpp:192-197,
 // direct.cpp:235, volpath.cpp: emitter->isOnSurface() is false).  Per-emitter
-// constants come from the host (scene_build.cpp configure_delta,
+// constants come from the host (configure_emitter.cpp configure_delta,
 // directional_bsphere) in an MtsgDelta record.
 #pragma once
 #include "dmath.h"

@@ -295,7 +295,7 @@ __device__ __forceinline__ float env_pdf_direction(glb_env *E, f3 d) { return en
 
 // A miss's evalEnvironment value (evalBilinear at level 0, mipmap.h:500-522) and
 // its internalPdfDirection (envmap.cpp:606-633) at the same (u, v), in one call:
-// both read the same four texels (level 0 is w0 x h0, scene_build.cpp), and each
+// both read the same four texels (level 0 is w0 x h0, configure_emitter.cpp), and each
 // result keeps its own summation order
 struct EnvValPdf { f3 value; float pdf; };
 ENV_CALL EnvValPdf env_eval_pdf_at(glb_env *E, EnvUV c) {

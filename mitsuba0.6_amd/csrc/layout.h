@@ -1,5 +1,5 @@
 // layout.h -- HBM layout of a configured scene, shared by the host builder
-// (scene_build.cpp) and the gfx950 kernels (path_kernel.hip).
+// (scene_build.cpp and its configure units) and the gfx950 kernels (path_kernel.hip).
 //
 // Everything is flat SoA/AoS arrays addressed by 32-bit indices:
 //   nodes     BVH2, 64 B per node, both children's boxes in one node (one
@@ -389,7 +389,7 @@ struct MtsgLaunch {
     uint32_t run_dq, run_dr;               // lanes / num_pixels and lanes % num_pixels of the megakernel's grid
     uint32_t one_emitter;                  // the emitter CDF is {0.0f, 1.0f} bit for bit: emitter 0 with pdf 1
     const float *face_n;                   // 3 per primitive: unit face normals, staged in LDS with a small scene
-                                           // (HitSrc<true>::fn; scene_build.cpp mtsg_face_normal)
+                                           // (HitSrc<true>::fn; configure_shape.cpp mtsg_face_normal)
     uint32_t lens;                         // kernel variant: the sensor is not `perspective` (the MTSG_FEAT_SET_LENS
                                            // kernels; host side only, like `delta`)
     MtsgCameraLens cam_lens;               // the camera's sensor type, aperture and focus plane (those kernels only)

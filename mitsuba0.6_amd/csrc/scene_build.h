@@ -1,6 +1,9 @@
 // scene_build.h -- host-side configure() of a Mitsuba scene description into
 // the HBM layout of layout.h (normals, tangents, TriAccel, emitter CDFs,
-// camera matrices, filter LUT, Sobol tables, BVH).
+// camera matrices, filter LUT, Sobol tables, BVH).  The public surface of the
+// host configure units: mtsg_configure_scene (scene_build.cpp) runs the stages of
+// configure_sensor.cpp, configure_bsdf.cpp, configure_emitter.cpp, configure_shape.cpp
+// and bvh_build.cpp (scene_build_impl.h); the rest is named where it is declared.
 #pragma once
 #include <stdint.h>
 
@@ -62,13 +65,13 @@ struct HostScene {
 
 // Returns MTSGPU_OK or an error code; `err` receives the message.
 int mtsg_configure_scene(const mtsgpu_scene_desc *desc, HostScene &out, std::string &err);
-// the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dpath.h)
+// the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dpath.h); configure_shape.cpp
 void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n);
-bool mtsg_invert4(const float *m16, float *inv16);   // Matrix4x4::invert, row-major
-void mtsg_build_qnodes(HostScene &S);   // host export only (mtsgpu_bvh_host)
-int mtsg_configure_filter(int32_t type, float param, MtsgFilter &f, std::string &err);
+bool mtsg_invert4(const float *m16, float *inv16);   // Matrix4x4::invert, row-major; configure_shape.cpp
+void mtsg_build_qnodes(HostScene &S);   // host export only (mtsgpu_bvh_host); bvh_build.cpp
+int mtsg_configure_filter(int32_t type, float param, MtsgFilter &f, std::string &err);   // configure_filter.cpp
 // Sobol: 1024 x 52 matrices regenerated from the Joe-Kuo parameters, and the
-// look_up GF(2) tables for resolution 2^m.
+// look_up GF(2) tables for resolution 2^m.  sobol_host.cpp
 const std::vector<uint32_t> &mtsg_sobol_matrices();
 void mtsg_sobol_lookup_table(uint32_t m, MtsgLookup &lut);
 void mtsg_sobol_lookup_solve(uint32_t m, MtsgLookup &lut);

@@ -2672,7 +2672,7 @@ static void compute_uv_tangents(Mesh *m) { /* trimesh.cpp:683-739 */
 typedef struct { float c[3]; float bmin[3], bmax[3]; } PrimBox;
 
 /* absolute part of the node boxes' conservative inflation: 1e-7 of the scene diagonal (as
-   scene_build.cpp's Builder::absEps).  A box of zero extent at coordinate 0 -- a floor at
+   bvh_build.cpp's Builder::absEps).  A box of zero extent at coordinate 0 -- a floor at
    y = 0 -- gets no relative inflation at all, and its slab t can round one ulp beyond the
    TriAccel t of a triangle it holds: without this the traversal could cull an exact-t tie
    partner (C4's coplanar hall and floor meshes), and the closest hit would depend on the

@@ -31,7 +31,7 @@ def float_boxes(n):
 def collapse(lo, hi, refs):
     """The 4-wide tree the host must have built from the BVH2: node 0 is the
     root; an inner BVH2 child is replaced by its two children; nodes are
-    numbered in depth-first preorder (scene_build.cpp QCollapse).  Returns, per
+    numbered in depth-first preorder (bvh_build.cpp QCollapse).  Returns, per
     4-wide node, its children as (box lo, box hi, ref) with inner refs renumbered."""
     out = []
 

@@ -92,7 +92,7 @@ print('fresh group ok')
 def test_group_first_upload_in_fresh_process():
     """the first upload of a process going through a group builds
     the Sobol tables on several host threads at once (capi.cpp
-    sobol_nibble_tables, scene_build.cpp mtsg_sobol_matrices).  Run it in a
+    sobol_nibble_tables, sobol_host.cpp mtsg_sobol_matrices).  Run it in a
     fresh child process, with no prior single-context upload."""
     import os
     import subprocess

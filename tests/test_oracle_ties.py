@@ -9,7 +9,7 @@ slab t rounded one ulp beyond the TriAccel t: the oracle culled the leaf holding
 3644 once 693 was found and returned 693, while every GPU engine returned 3644
 (tests/test_gpu_bench_kernels.py found the one sample whose path this changed;
 tools/diag_c4_ray.py).  The boxes now carry the same absolute inflation as the
-product's builder (1e-7 of the scene diagonal, scene_build.cpp Builder::absEps).
+product's builder (1e-7 of the scene diagonal, bvh_build.cpp Builder::absEps).
 """
 import ctypes as C
 

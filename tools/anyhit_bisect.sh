@@ -12,11 +12,12 @@ cd "$(dirname "$0")/../mitsuba0.6_amd/csrc"
 OUT=../_build
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
    -fno-gpu-flush-denormals-to-zero -I$OUT -DMTSG_ANYHIT_INLINE"
+# the main build's objects in link order, path_kernel.o replaced by the variant's
+objs() { make -s print-objs | sed "s|$OUT/path_kernel.o|$1|"; }
 mkdir -p $OUT/variants/bis
 for n in "$@"; do
   (/opt/rocm/bin/hipcc $F -mllvm -opt-bisect-limit=$n -c path_kernel.hip -o $OUT/variants/bis/pk_$n.o 2> /dev/null &&
-   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/variants/libmtsgpu_bis$n.so $OUT/capi.o $OUT/group.o \
-       $OUT/kdtree_build.o $OUT/scene_build.o $OUT/rtrans_host.o $OUT/variants/bis/pk_$n.o $OUT/film_kernel.o \
-       $OUT/probe_kernel.o && echo "bis$n ok") &
+   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/variants/libmtsgpu_bis$n.so \
+       $(objs $OUT/variants/bis/pk_$n.o) && echo "bis$n ok") &
 done
 wait
