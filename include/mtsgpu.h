@@ -58,8 +58,14 @@ enum { /* BSDF plugins on the path (src/bsdfs) */
     MTSGPU_BSDF_CONDUCTOR = 4,       /* conductor.cpp  (smooth, delta reflection)        */
     MTSGPU_BSDF_DIELECTRIC = 5,      /* dielectric.cpp (smooth, delta refl. + transm.)   */
     MTSGPU_BSDF_PLASTIC = 6,         /* plastic.cpp    (delta coating + diffuse base)    */
-    MTSGPU_BSDF_TWOSIDED = 7         /* twosided.cpp   (wraps nested[0], nested[1])      */
+    MTSGPU_BSDF_TWOSIDED = 7,        /* twosided.cpp   (wraps nested[0], nested[1])      */
+    /* combinators.  One chain is supported: [mask] -> [twosided] -> [mixturebsdf | blendbsdf]
+       -> leaf, every level optional; mtsgpu_check_scene / mtsgpu_upload_scene refuse the rest */
+    MTSGPU_BSDF_MIXTURE = 8,         /* mixturebsdf.cpp (weighted sum of children[])      */
+    MTSGPU_BSDF_BLEND = 9,           /* blendbsdf.cpp   (nested[0], nested[1] by 'weight') */
+    MTSGPU_BSDF_MASK = 10            /* mask.cpp        ('opacity' in front of nested[0])  */
 };
+#define MTSGPU_MIXTURE_MAX 8         /* children of one mixturebsdf */
 
 enum { /* MicrofacetDistribution::EType (src/bsdfs/microfacet.h:48-57) */
     MTSGPU_DISTR_BECKMANN = 0,
@@ -105,6 +111,25 @@ typedef struct {
        nested BSDFs must be one-sided reflectors (diffuse, roughconductor,
        roughplastic, conductor, plastic): TwoSidedBRDF::configure raises otherwise */
     int32_t nested[2];
+    /* ---- appended for the combinators; the struct grew at its end, no earlier offset
+       moved and MTSGPU_ABI_VERSION stays 8 (a caller built against the shorter struct
+       never sets types 8-10, and no other type reads these fields) ---- */
+    /* mixturebsdf (mixturebsdf.cpp:115-172): the nested BSDFs in order and the 'weights'
+       string's numbers; configure raises unless the counts match and the sum is > 0, and
+       rescales by 1 / sum when ensure_energy_conservation is set and the sum exceeds 1.
+       Children: diffuse, roughconductor, roughplastic, and at most one of conductor,
+       plastic, dielectric (blendbsdf's nested[]: the same rule) */
+    int32_t num_children, num_weights;
+    int32_t children[MTSGPU_MIXTURE_MAX];
+    float weights[MTSGPU_MIXTURE_MAX];
+    /* blendbsdf (blendbsdf.cpp:60-75): 'weight' (default 0.5) or a texture of that name;
+       nested[0], nested[1] are both required */
+    float weight;
+    mtsgpu_texture_desc weight_tex;
+    /* mask (mask.cpp:74-111): 'opacity' (default 0.5) or a texture of that name, in front
+       of nested[0]; ensure_energy_conservation scales an opacity above 1 */
+    float opacity[3];
+    mtsgpu_texture_desc opacity_tex;
 } mtsgpu_bsdf_desc;
 
 enum { MTSGPU_EMITTER_AREA = 0,      /* area.cpp: on a shape (mesh_desc.emitter)          */
@@ -507,6 +532,14 @@ int mtsgpu_develop_ldr_device(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *
  * (roughplastic.cpp:309-315), -1 for a textured alpha (evaluated per hit), 1 for
  * diffuse, 0 for every other BSDF.  factors: num_bsdfs floats. */
 int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, char *msg, size_t cap);
+/* (a scene with a mixturebsdf, blendbsdf or mask: MTSGPU_EINVAL, like the `albedo` field) */
+/* Host-only (no device needed): configure `scene` and copy what configure() derived for the
+ * combinator BSDF `bsdf` (types 8-10): out21[0] = children, [1..8] the mixture's m_weights
+ * after the rescale, [9..17] m_pdf's CDF (pmf.h append + normalize), [18..20] the blend's
+ * constant weight (x3) or the mask's opacity after ensureEnergyConservation; *flags (may be
+ * NULL) its type flags, BSDF::EBSDFType bits.  Another BSDF type: MTSGPU_EINVAL. */
+int mtsgpu_combo_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out21, int32_t *flags, char *msg,
+                      size_t cap);
 /* Batch ray queries on the uploaded scene, one GPU lane per ray:
  * Scene::rayIntersect (closest hit, shadow = 0) or the occlusion test
  * (shadow = 1) of ShapeKDTree::rayIntersect (src/librender/skdtree.cpp:

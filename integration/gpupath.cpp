@@ -442,9 +442,10 @@ private:
         const std::string hint = shape->getID() == "unnamed"
             ? "a mesh of a compound shape (OBJ / serialized file) does not carry its <shape>'s id: give the BSDF "
               "itself an id (<bsdf id=...>, or a <ref> to one) in " : "give the BSDF (or its shape) an id in ";
-        if (p.getPluginName() == "twosided")
-            Log(EError, "twosided BSDF \"%s\" %s: its nested BSDFs are read from the scene file, which does not "
-                "hold it; %s%s", bsdf->getID().c_str(), where.c_str(), hint.c_str(),
+        if (p.getPluginName() == "twosided" || p.getPluginName() == "mixturebsdf" || p.getPluginName() == "blendbsdf" ||
+            p.getPluginName() == "mask")
+            Log(EError, "%s BSDF \"%s\" %s: its nested BSDFs are read from the scene file, which does not "
+                "hold it; %s%s", p.getPluginName().c_str(), bsdf->getID().c_str(), where.c_str(), hint.c_str(),
                 m_sceneFile.empty() ? "a scene file" : m_sceneFile.string().c_str());
         if (!isConstant(bsdf))
             Log(EError, "BSDF \"%s\" %s has a textured parameter, and textures are read from the scene file, which "
@@ -579,7 +580,59 @@ private:
             }
             return idx;
         }
-        if (!nested.empty()) Log(EError, "%s: nested BSDFs are only supported inside twosided", nodes[k].plugin);
+        const std::string plugin = p.getPluginName();
+        if (plugin == "mixturebsdf" || plugin == "blendbsdf" || plugin == "mask") {
+            /* mixturebsdf.cpp:67-98, blendbsdf.cpp:60-75, mask.cpp:74-78.  The library walks one chain,
+               [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf, and refuses the rest with
+               MTSGPU_EINVAL at upload (mtsgpu_upload_scene's message names the plugin); what the
+               descriptor itself cannot hold is an error here */
+            mtsgpu_bsdf_desc d;
+            std::memset(&d, 0, sizeof d);
+            d.nested[0] = d.nested[1] = -1;
+            d.ensure_energy_conservation = p.getBoolean("ensureEnergyConservation", true) ? 1 : 0;
+            if (plugin == "mixturebsdf") {
+                d.type = MTSGPU_BSDF_MIXTURE;
+                std::vector<std::string> w = tokenize(p.getString("weights", ""), " ,;");
+                if (w.empty()) Log(EError, "No weights were supplied!");
+                if (w.size() > MTSGPU_MIXTURE_MAX || nested.size() > MTSGPU_MIXTURE_MAX)
+                    Log(EError, "mixturebsdf: more than %d nested BSDFs are not supported", MTSGPU_MIXTURE_MAX);
+                for (size_t j = 0; j < w.size(); ++j) {
+                    char *end = NULL;
+                    d.weights[j] = (float) strtod(w[j].c_str(), &end);
+                    if (*end != '\0') Log(EError, "Could not parse the BSDF weights!");
+                }
+                d.num_weights = (int32_t) w.size();
+                d.num_children = (int32_t) nested.size();
+            } else if (plugin == "blendbsdf") {
+                d.type = MTSGPU_BSDF_BLEND;
+                if (nested.size() != 2) Log(EError, "BSDF count mismatch: expected two nested BSDF instances!");
+                d.weight = (float) p.getFloat("weight", 0.5f);
+            } else {
+                d.type = MTSGPU_BSDF_MASK;
+                if (nested.size() != 1) Log(EError, "mask: exactly one nested BSDF is required");
+                const Spectrum o = p.getSpectrum("opacity", Spectrum(0.5f));
+                Float r, g, b;
+                o.toLinearRGB(r, g, b);
+                d.opacity[0] = (float) r; d.opacity[1] = (float) g; d.opacity[2] = (float) b;
+            }
+            for (size_t j = 0; j < tex.size(); ++j) {
+                if (plugin == "blendbsdf" && tex[j].first == "weight") d.weight_tex = tex[j].second;
+                else if (plugin == "mask" && tex[j].first == "opacity") d.opacity_tex = tex[j].second;
+                else Log(EError, "%s: unsupported texture parameter \"%s\"", plugin.c_str(), tex[j].first.c_str());
+            }
+            const int idx = (int) m_bsdfs.size();
+            m_bsdfs.push_back(d);
+            m_bsdfObjs.push_back(obj);
+            for (size_t j = 0; j < nested.size(); ++j) {
+                const int ni = xmlNode(nodes, props, nested[j], NULL);
+                if (plugin == "mixturebsdf") m_bsdfs[idx].children[j] = ni;
+                else m_bsdfs[idx].nested[j] = ni;
+            }
+            return idx;
+        }
+        if (!nested.empty())
+            Log(EError, "%s: nested BSDFs are only supported inside twosided, mixturebsdf, blendbsdf and mask",
+                nodes[k].plugin);
         return appendDesc(p, obj, &tex);
     }
 

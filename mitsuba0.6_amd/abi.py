@@ -13,6 +13,8 @@ STATUS_NAMES = {OK: 'OK', EINVAL: 'EINVAL', EHIP: 'EHIP', ENOMEM: 'ENOMEM', ESTA
 
 BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR, BSDF_ROUGHDIELECTRIC, BSDF_ROUGHPLASTIC = 0, 1, 2, 3
 BSDF_CONDUCTOR, BSDF_DIELECTRIC, BSDF_PLASTIC, BSDF_TWOSIDED = 4, 5, 6, 7
+BSDF_MIXTURE, BSDF_BLEND, BSDF_MASK = 8, 9, 10
+MIXTURE_MAX = 8
 TEX_NONE, TEX_CHECKERBOARD = 0, 1
 ABI_VERSION = 8
 TRACE_SHADOW, TRACE_KDTREE = 1, 2           # mtsgpu_trace_rays_ex flags
@@ -53,7 +55,12 @@ class BsdfDesc(C.Structure):
                 ('diffuse_reflectance', _f3), ('nonlinear', C.c_int32),
                 ('rtrans_data', C.c_void_p), ('rtrans_bytes', C.c_uint64),
                 ('reflectance_tex', TextureDesc), ('alpha_tex', TextureDesc),
-                ('nested', C.c_int32 * 2)]
+                ('nested', C.c_int32 * 2),
+                # appended for mixturebsdf / blendbsdf / mask (the struct grew at its end)
+                ('num_children', C.c_int32), ('num_weights', C.c_int32),
+                ('children', C.c_int32 * MIXTURE_MAX), ('weights', C.c_float * MIXTURE_MAX),
+                ('weight', C.c_float), ('weight_tex', TextureDesc),
+                ('opacity', _f3), ('opacity_tex', TextureDesc)]
 
 
 class EmitterDesc(C.Structure):

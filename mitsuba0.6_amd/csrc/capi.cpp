@@ -61,6 +61,7 @@ struct mtsgpu_ctx {
     DevBuf nodes, hnodes, tris, prim_vtx, dpdu, positions, normals, shapes, bsdfs, emitters, area_cdf, em_cdf, sobol;
     DevBuf env, env_texels, env_rows, env_cols, env_weights, env_grows, env_gcols;
     DevBuf rtrans, texcoords, analytic, delta;
+    DevBuf combos;   // mixturebsdf / blendbsdf / mask records (MtsgLaunch::combos)
     DevBuf qrays, qhits;      // mtsgpu_trace_rays staging
     DevBuf film_own, film_spill, samples, counters, contrib;
     DevBuf dev_in, dev_out;   // staging of mtsgpu_develop (host film -> developed image)
@@ -95,7 +96,7 @@ const std::string &launch_layout_error() {
             {"field_kernel", mtsg_launch_bytes_field_kernel()},
 #define MTSG_BYTES_ROW(N) {"path_f" #N, mtsg_launch_bytes_path_f##N()}, {"wf_shade_f" #N, mtsg_launch_bytes_wf_shade_f##N()},
             MTSG_BYTES_ROW(0) MTSG_BYTES_ROW(1) MTSG_BYTES_ROW(2) MTSG_BYTES_ROW(3) MTSG_BYTES_ROW(6) MTSG_BYTES_ROW(7)
-            MTSG_BYTES_ROW(1031) MTSG_BYTES_ROW(3079)
+            MTSG_BYTES_ROW(1031) MTSG_BYTES_ROW(3079) MTSG_BYTES_ROW(7175)
 #undef MTSG_BYTES_ROW
         };
         for (const auto &o : objs)
@@ -108,6 +109,11 @@ const std::string &launch_layout_error() {
 }
 
 int ensure_kdtree(mtsgpu_ctx *ctx);   // the reference's SAH kd-tree, built on first use (below)
+
+// the `albedo` field and mtsgpu_albedo_factors_host over a scene with combinator BSDFs
+const char *mtsg_albedo_combo_error() {
+    return "the 'albedo' field is not supported in a scene with a mixturebsdf, blendbsdf or mask BSDF";
+}
 
 int fail(mtsgpu_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->err = msg;
@@ -245,7 +251,8 @@ int mtsgpu_upload_scene(mtsgpu_ctx *ctx, const mtsgpu_scene_desc *scene) {
     if ((!H.rtrans.empty() && (e = upload(ctx->rtrans, H.rtrans, s)) != hipSuccess) ||
         (!H.texcoords.empty() && (e = upload(ctx->texcoords, H.texcoords, s)) != hipSuccess) ||
         (!H.analytic.empty() && (e = upload(ctx->analytic, H.analytic, s)) != hipSuccess) ||
-        (!H.deltas.empty() && (e = upload(ctx->delta, H.deltas, s)) != hipSuccess))
+        (!H.deltas.empty() && (e = upload(ctx->delta, H.deltas, s)) != hipSuccess) ||
+        (!H.combos.empty() && (e = upload(ctx->combos, H.combos, s)) != hipSuccess))
         return hip_fail(ctx, e, "texture/table upload");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "scene upload sync");
     MtsgDeviceScene &D = ctx->dscene;
@@ -418,6 +425,7 @@ int render_buffers(RenderRun &R, float *film_dev) {
     L.face_n = (const float *)ctx->face_n.p;
     L.sobol_nib = (const uint32_t *)ctx->sobol.p;
     L.scan_tris = (const MtsgTri *)ctx->scan_tris.p;
+    L.combos = ctx->host.combos.empty() ? nullptr : (const MtsgCombo *)ctx->combos.p;
     L.film_own = R.own;
     L.film_spill = (double *)ctx->film_spill.p;
     L.samples = p.nsamp ? (float *)ctx->samples.p : nullptr;
@@ -653,6 +661,11 @@ int field_job_check(mtsgpu_ctx *ctx, const mtsgpu_field_desc *fields, uint32_t n
         if (fields[f].field < 0 || fields[f].field >= MTSGPU_FIELD_COUNT)
             return fail(ctx, MTSGPU_EINVAL, "Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', "
                                             "'geoNormal', 'shNormal', 'primIndex', 'shapeIndex', or 'uv'!");
+    // getDiffuseReflectance of a mixturebsdf / blendbsdf / mask is not restated: the field pass
+    // (field_kernel.hip field_albedo) knows the leaves and twosided only
+    for (uint32_t f = 0; f < n; ++f)
+        if (fields[f].field == MTSGPU_FIELD_ALBEDO && ctx->have_scene && !ctx->host.combos.empty())
+            return fail(ctx, MTSGPU_EINVAL, mtsg_albedo_combo_error());
     return MTSGPU_OK;
 }
 }  // namespace
@@ -864,12 +877,37 @@ int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, c
         if (msg && cap) std::snprintf(msg, cap, "%s", err.c_str());
         return rc;
     }
+    if (!H.combos.empty()) {   // (the `albedo` field refuses such a scene too: field_job_check, below)
+        if (msg && cap) std::snprintf(msg, cap, "%s", mtsg_albedo_combo_error());
+        return MTSGPU_EINVAL;
+    }
     for (uint32_t i = 0; i < scene->num_bsdfs; ++i) {
         const MtsgBsdf &b = H.bsdfs[i];
         factors[i] = b.type == MTSGPU_BSDF_DIFFUSE ? 1.0f
                    : b.type == MTSGPU_BSDF_PLASTIC ? 1 - b.fdr_ext
                    : b.type == MTSGPU_BSDF_ROUGHPLASTIC ? (b.alpha_tex.type ? -1.0f : b.ftr_ext) : 0.0f;
     }
+    return MTSGPU_OK;
+}
+
+int mtsgpu_combo_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out21, int32_t *flags, char *msg,
+                      size_t cap) {
+    if (!scene || !out21) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    int rc = mtsg_configure_scene(scene, H, err);
+    if (!rc && (bsdf >= scene->num_bsdfs || H.bsdfs[bsdf].type < MTSGPU_BSDF_MIXTURE)) {
+        err = "mtsgpu_combo_host: not a mixturebsdf, blendbsdf or mask";
+        rc = MTSGPU_EINVAL;
+    }
+    if (msg && cap) std::snprintf(msg, cap, "%s", err.c_str());
+    if (rc) return rc;
+    const MtsgCombo &c = H.combos[H.bsdfs[bsdf].nested[0]];
+    out21[0] = (float)c.n;
+    std::memcpy(out21 + 1, c.w, sizeof c.w);
+    std::memcpy(out21 + 9, c.cdf, sizeof c.cdf);
+    std::memcpy(out21 + 18, c.value, sizeof c.value);
+    if (flags) *flags = H.bsdfs[bsdf].flags;
     return MTSGPU_OK;
 }
 
@@ -882,7 +920,7 @@ void mtsgpu_destroy(mtsgpu_ctx *ctx) {
                       &ctx->shapes, &ctx->bsdfs, &ctx->emitters, &ctx->area_cdf, &ctx->em_cdf, &ctx->sobol,
                       &ctx->film_own, &ctx->film_spill, &ctx->samples, &ctx->counters, &ctx->contrib,
                       &ctx->env, &ctx->env_texels, &ctx->env_rows, &ctx->env_cols, &ctx->env_weights, &ctx->env_grows, &ctx->env_gcols,
-                      &ctx->rtrans, &ctx->texcoords, &ctx->delta, &ctx->qrays, &ctx->qhits, &ctx->field_first,
+                      &ctx->rtrans, &ctx->texcoords, &ctx->delta, &ctx->combos, &ctx->qrays, &ctx->qhits, &ctx->field_first,
                       &ctx->dev_in, &ctx->dev_out, &ctx->ldr_scratch, &ctx->wf_state, &ctx->wf_ray, &ctx->wf_rslot, &ctx->wf_cls,
                       &ctx->wf_cnt, &ctx->wf_hit, &ctx->wf_hitrec, &ctx->wf_occl, &ctx->wf_live, &ctx->wf_ovf, &ctx->wf_part, &ctx->wf_kind, &ctx->rp_order, &ctx->rp_start, &ctx->rp_sfmt, &ctx->env_grows, &ctx->env_gcols};
     for (DevBuf *b : bufs) b->release();

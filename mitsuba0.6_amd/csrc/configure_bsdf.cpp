@@ -248,6 +248,8 @@ int configure_bsdf(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::vector<float> &r
     b.type = d.type;
     b.nested[0] = b.nested[1] = -1;
     if (d.type == MTSGPU_BSDF_TWOSIDED) return MTSGPU_OK;   // resolved by configure_twosided
+    if (d.type == MTSGPU_BSDF_MIXTURE || d.type == MTSGPU_BSDF_BLEND || d.type == MTSGPU_BSDF_MASK)
+        return MTSGPU_OK;                                   // resolved by configure_combo / configure_mask
     if (d.type == MTSGPU_BSDF_CONDUCTOR || d.type == MTSGPU_BSDF_DIELECTRIC || d.type == MTSGPU_BSDF_PLASTIC)
         return configure_smooth(d, b, err);
     if (d.type == MTSGPU_BSDF_DIFFUSE) {
@@ -313,6 +315,7 @@ int configure_twosided(const mtsgpu_bsdf_desc &d, int nb, const std::vector<Mtsg
     for (int k = 0; k < 2; ++k) {
         const MtsgBsdf &c = bsdfs[n[k]];
         if (c.type == MTSGPU_BSDF_TWOSIDED) { err = "twosided: nesting a twosided BSDF is not supported"; return MTSGPU_EINVAL; }
+        if (c.type == MTSGPU_BSDF_MASK) { err = "twosided: nesting a mask BSDF is not supported (mask wraps the chain)"; return MTSGPU_EINVAL; }
         const uint32_t lobes = (uint32_t)c.flags & ~(uint32_t)(MTSG_F_FRONT | MTSG_F_BACK);
         if (lobes) flags |= lobes | (k == 0 ? MTSG_F_FRONT : MTSG_F_BACK);
     }
@@ -320,6 +323,120 @@ int configure_twosided(const mtsgpu_bsdf_desc &d, int nb, const std::vector<Mtsg
     b.flags = (int32_t)flags;
     b.nested[0] = n[0];
     b.nested[1] = n[1];
+    return MTSGPU_OK;
+}
+
+const char *plugin_name(int type) {
+    static const char *names[] = {"diffuse", "roughconductor", "roughdielectric", "roughplastic", "conductor", "dielectric",
+                                  "plastic", "twosided", "mixturebsdf", "blendbsdf", "mask"};
+    return type >= 0 && type <= MTSGPU_BSDF_MASK ? names[type] : "?";
+}
+
+int refuse(std::string &err, const char *plugin, const std::string &what) {
+    err = std::string(plugin) + ": " + what;
+    return MTSGPU_EINVAL;
+}
+
+// MixtureBSDF::configure (mixturebsdf.cpp:115-172) and BlendBSDF's constructor and configure
+// (blendbsdf.cpp:60-75, 101-133) into the side table; the record's flags are its children's.
+// The device walks one chain (dcombo.h): children are leaves, none a roughdielectric (its
+// sample() draws a 1D number inside the chosen branch only), at most one with a delta lobe
+int configure_combo(const mtsgpu_bsdf_desc &d, int nb, const std::vector<MtsgBsdf> &bsdfs, MtsgBsdf &b,
+                    std::vector<MtsgCombo> &combos, std::string &err) {
+    const char *me = plugin_name(d.type);
+    MtsgCombo c;
+    std::memset(&c, 0, sizeof c);
+    c.type = d.type;
+    int rc;
+    if (d.type == MTSGPU_BSDF_MIXTURE) {
+        if (d.num_children < 0 || d.num_children > MTSGPU_MIXTURE_MAX || d.num_weights > MTSGPU_MIXTURE_MAX)
+            return refuse(err, me, "more than 8 nested BSDFs are not supported");
+        if (d.num_weights <= 0) return refuse(err, me, "No weights were supplied!");
+        if (d.num_children != d.num_weights)
+            return refuse(err, me, "BSDF count mismatch: " + std::to_string(d.num_children) + " bsdfs, but specified " +
+                                       std::to_string(d.num_weights) + " weights");
+        c.n = d.num_children;
+        float totalWeight = 0;
+        for (int i = 0; i < c.n; ++i) {
+            if (d.weights[i] < 0) return refuse(err, me, "Invalid BSDF weight!");
+            totalWeight += d.weights[i];
+        }
+        if (totalWeight <= 0) return refuse(err, me, "The weights must sum to a value greater than zero!");
+        for (int i = 0; i < c.n; ++i) c.w[i] = d.weights[i];
+        if (d.ensure_energy_conservation && totalWeight > 1) {
+            const float scale = 1.0f / totalWeight;
+            for (int i = 0; i < c.n; ++i) c.w[i] *= scale;
+        }
+        // m_pdf: DiscreteDistribution::append per child, then normalize() (pmf.h:52-58, 101-114)
+        c.cdf[0] = 0.0f;
+        for (int i = 0; i < c.n; ++i) c.cdf[i + 1] = c.cdf[i] + c.w[i];
+        const float sum = c.cdf[c.n];
+        if (sum > 0) {
+            const float normalization = 1.0f / sum;
+            for (int i = 1; i <= c.n; ++i) c.cdf[i] *= normalization;
+            c.cdf[c.n] = 1.0f;
+        }
+        for (int i = 0; i < c.n; ++i) c.child[i] = d.children[i];
+    } else {
+        if (d.nested[0] < 0 || d.nested[1] < 0)
+            return refuse(err, me, "BSDF count mismatch: expected two nested BSDF instances!");
+        c.n = 2;
+        c.child[0] = d.nested[0];
+        c.child[1] = d.nested[1];
+        c.value[0] = c.value[1] = c.value[2] = d.weight;
+        if ((rc = set_tex(d.weight_tex, 1.0f, c.tex, err))) return rc;
+    }
+    uint32_t flags = 0;
+    int deltas = 0;
+    for (int i = 0; i < c.n; ++i) {
+        if (c.child[i] < 0 || c.child[i] >= nb) return refuse(err, me, "nested BSDF index out of range");
+        const MtsgBsdf &cb = bsdfs[c.child[i]];
+        if (cb.type >= MTSGPU_BSDF_TWOSIDED)
+            return refuse(err, me, std::string("nesting a '") + plugin_name(cb.type) +
+                                       "' BSDF is not supported (the chain is [mask] -> [twosided] -> [mixturebsdf | "
+                                       "blendbsdf] -> leaf)");
+        if (cb.type == MTSGPU_BSDF_ROUGHDIELECTRIC)
+            return refuse(err, me, "a nested 'roughdielectric' BSDF is not supported");
+        if (cb.flags & (MTSG_F_DELTA_REFL | MTSG_F_DELTA_TRANS)) ++deltas;
+        flags |= (uint32_t)cb.flags;
+    }
+    if (deltas > 1)
+        return refuse(err, me, "more than one nested BSDF with a delta lobe (conductor, plastic, dielectric) is not supported");
+    // (BlendBSDF::configure pushes the children's types as they are, blendbsdf.cpp:119-131: a
+    //  textured weight adds no ESpatiallyVarying there, unlike Mask's opacity)
+    b.flags = (int32_t)flags;
+    b.nested[0] = (int32_t)combos.size();
+    combos.push_back(c);
+    return MTSGPU_OK;
+}
+
+// Mask's constructor and configure (mask.cpp:74-111): the nested BSDF's lobes plus the null
+// lobe, on both sides; opacity through ensureEnergyConservation(opacity, "opacity", 1.0f)
+int configure_mask(const mtsgpu_bsdf_desc &d, int nb, const std::vector<MtsgBsdf> &bsdfs, MtsgBsdf &b,
+                   std::vector<MtsgCombo> &combos, std::string &err) {
+    if (d.nested[0] < 0) return refuse(err, "mask", "A child BSDF is required");
+    if (d.nested[0] >= nb) return refuse(err, "mask", "nested BSDF index out of range");
+    const MtsgBsdf &cb = bsdfs[d.nested[0]];
+    if (cb.type == MTSGPU_BSDF_MASK) return refuse(err, "mask", "nesting a 'mask' BSDF is not supported");
+    bool rd = cb.type == MTSGPU_BSDF_ROUGHDIELECTRIC;
+    if (cb.type == MTSGPU_BSDF_TWOSIDED)   // (a mixture's or blend's children were checked where it was configured)
+        for (int k = 0; k < 2; ++k) rd |= bsdfs[cb.nested[k]].type == MTSGPU_BSDF_ROUGHDIELECTRIC;
+    if (rd) return refuse(err, "mask", "a nested 'roughdielectric' BSDF is not supported");
+    MtsgCombo c;
+    std::memset(&c, 0, sizeof c);
+    c.type = d.type;
+    c.n = 1;
+    c.child[0] = d.nested[0];
+    float mx[3];
+    tex_max(d.opacity_tex, d.opacity, mx);
+    const float sc = energy_scale(mx, d.ensure_energy_conservation);
+    for (int i = 0; i < 3; ++i) c.value[i] = sc != 1.0f ? d.opacity[i] * sc : d.opacity[i];
+    int rc;
+    if ((rc = set_tex(d.opacity_tex, sc, c.tex, err))) return rc;
+    // extraFlags = ESpatiallyVarying on every component when the opacity is not constant (mask.cpp:98-106)
+    b.flags = cb.flags | MTSG_F_NULL | MTSG_F_FRONT | MTSG_F_BACK | (c.tex.type ? MTSG_F_SPATIALLY_VARYING : 0);
+    b.nested[0] = (int32_t)combos.size();
+    combos.push_back(c);
     return MTSGPU_OK;
 }
 
@@ -333,9 +450,18 @@ int configure_bsdfs(const mtsgpu_scene_desc &D, HostScene &S, std::string &err) 
     S.bsdfs.resize(nb + 2);
     for (uint32_t i = 0; i < nb; ++i)
         if ((rc = configure_bsdf(D.bsdfs[i], S.bsdfs[i], S.rtrans, err))) return rc;
+    // the wrappers inside out: mixture / blend over leaves, twosided over those, mask over all
+    for (uint32_t i = 0; i < nb; ++i)
+        if ((D.bsdfs[i].type == MTSGPU_BSDF_MIXTURE || D.bsdfs[i].type == MTSGPU_BSDF_BLEND) &&
+            (rc = configure_combo(D.bsdfs[i], (int)nb, S.bsdfs, S.bsdfs[i], S.combos, err)))
+            return rc;
     for (uint32_t i = 0; i < nb; ++i)
         if (D.bsdfs[i].type == MTSGPU_BSDF_TWOSIDED &&
             (rc = configure_twosided(D.bsdfs[i], (int)nb, S.bsdfs, S.bsdfs[i], err)))
+            return rc;
+    for (uint32_t i = 0; i < nb; ++i)
+        if (D.bsdfs[i].type == MTSGPU_BSDF_MASK &&
+            (rc = configure_mask(D.bsdfs[i], (int)nb, S.bsdfs, S.bsdfs[i], S.combos, err)))
             return rc;
     for (uint32_t i = 0; i < nb; ++i) {
         const MtsgBsdf &b = S.bsdfs[i];

@@ -179,12 +179,25 @@ int configure_analytic_shape(const mtsgpu_scene_desc &D, uint32_t si, HostScene 
 // ---- triangle meshes ---------------------------------------------------------
 // EAnisotropic (roughconductor.cpp:229-231) without texcoords: computeUVTangents error (trimesh.cpp:685-691)
 // (through twosided: its combined type carries the nested EAnisotropic)
+// the leaves below BSDF record `i`: through twosided and the combinators' chain (configure_bsdf.cpp)
+void leaf_bsdfs(const HostScene &S, int i, std::vector<int> &out) {
+    const MtsgBsdf &b = S.bsdfs[i];
+    if (b.type == MTSGPU_BSDF_TWOSIDED) {
+        leaf_bsdfs(S, b.nested[0], out);
+        leaf_bsdfs(S, b.nested[1], out);
+    } else if (b.type == MTSGPU_BSDF_MIXTURE || b.type == MTSGPU_BSDF_BLEND || b.type == MTSGPU_BSDF_MASK) {
+        const MtsgCombo &c = S.combos[b.nested[0]];
+        for (int k = 0; k < c.n; ++k) leaf_bsdfs(S, c.child[k], out);
+    } else {
+        out.push_back(i);
+    }
+}
+
 int check_tangents(const mtsgpu_scene_desc &D, const mtsgpu_mesh_desc &m, const HostScene &S, std::string &err) {
     bool aniso = false;
     if (m.bsdf >= 0) {
-        const mtsgpu_bsdf_desc *ub = &D.bsdfs[m.bsdf];
-        const int cand[2] = {ub->type == MTSGPU_BSDF_TWOSIDED ? S.bsdfs[m.bsdf].nested[0] : m.bsdf,
-                             ub->type == MTSGPU_BSDF_TWOSIDED ? S.bsdfs[m.bsdf].nested[1] : m.bsdf};
+        std::vector<int> cand;
+        leaf_bsdfs(S, m.bsdf, cand);
         for (int c : cand) {
             const mtsgpu_bsdf_desc &cb = D.bsdfs[c];
             if ((cb.type == MTSGPU_BSDF_ROUGHCONDUCTOR || cb.type == MTSGPU_BSDF_ROUGHDIELECTRIC) &&

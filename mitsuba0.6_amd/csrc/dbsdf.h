@@ -30,7 +30,8 @@ enum { DISTR_BECKMANN = 0, DISTR_GGX = 1, DISTR_PHONG = 2 };
 #define HELPER_CALL __device__ __noinline__
 #endif
 enum { BSDF_DIFFUSE = 0, BSDF_ROUGHCONDUCTOR = 1, BSDF_ROUGHDIELECTRIC = 2, BSDF_ROUGHPLASTIC = 3,
-       BSDF_CONDUCTOR = 4, BSDF_DIELECTRIC = 5, BSDF_PLASTIC = 6, BSDF_TWOSIDED = 7 };   // = MTSGPU_BSDF_*
+       BSDF_CONDUCTOR = 4, BSDF_DIELECTRIC = 5, BSDF_PLASTIC = 6, BSDF_TWOSIDED = 7,
+       BSDF_MIXTURE = 8, BSDF_BLEND = 9, BSDF_MASK = 10 };   // = MTSGPU_BSDF_* (8-10: dcombo.h)
 
 __device__ __forceinline__ float tan_theta(f3 v) {           // frame.h:117-122
     float temp = 1 - v.z * v.z;

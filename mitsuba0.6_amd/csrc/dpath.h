@@ -1171,6 +1171,7 @@ __device__ __forceinline__ f3 xf_point(const float *m, f3 p) {         // transf
 }
 
 #include "dsensor.h"   // the sensors' primary rays (the MTSG_FEAT_LENS kernels)
+#include "dcombo.h"    // mixturebsdf, blendbsdf, mask (the MTSG_FEAT_SET_COMBO kernels)
 
 __device__ __forceinline__ f3 area_Le(const MtsgDeviceScene &S, const Hit &h, f3 d) {   // area.cpp:104-109
     const MtsgEmitter &e = S.emitters[S.shapes[h.shape].emitter];
@@ -1440,6 +1441,14 @@ struct PathShader {
     // primary ray has its own origin and interval (StartRec::ro, mint, maxt), and produce()
     // draws the aperture sample where the sensor takes one
     static constexpr bool LENS = (FEAT & MTSG_FEAT_LENS) != 0;
+    // COMBO (MTSG_FEAT_COMBO): the scene holds a mixturebsdf, blendbsdf or mask (dcombo.h).  Its one
+    // feature set is the lens set's, which such a scene need not need: lens_ray() asks the sensor
+    // there and is the constant `true` in the lens set's own kernels
+    static constexpr bool COMBO = (FEAT & MTSG_FEAT_COMBO) != 0;
+    __device__ __forceinline__ bool lens_ray() const {
+        if constexpr (COMBO) return L.cam_lens.type != MTSG_SENSOR_PERSPECTIVE;
+        else return true;
+    }
     __device__ __forceinline__ bool have_env() const {
         if constexpr (DELTA) return L.scene.env_emitter >= 0;
         else return true;
@@ -1503,6 +1512,7 @@ struct PathShader {
         r.sx = (float)px + u;
         r.sy = (float)py + v;
         if constexpr (LENS) {
+            if (lens_ray()) {
             // renderBlock's aperture draw (integrator.cpp:171-172), then the sensor's ray
             float ax = 0.5f, ay = 0.5f;
             if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ax, ay);
@@ -1510,6 +1520,7 @@ struct PathShader {
             r.invZ = 1.0f;
             sensor_ray(S.cam, L.cam_lens, r.sx, r.sy, ax, ay, r.ro, r.rd, r.mint, r.maxt);
             return;
+            }
         }
         // PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298)
         const MtsgCamera &cam = S.cam;
@@ -1519,6 +1530,11 @@ struct PathShader {
         const float *W = cam.to_world;
         r.rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
                   W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
+        if constexpr (COMBO) {   // a `perspective` ray in the lens set's record: what load() forms elsewhere
+            r.ro = cam_origin();
+            r.mint = cam.near_clip * r.invZ;
+            r.maxt = cam.far_clip * r.invZ;
+        }
     }
 
     // every camera ray's origin (wave-uniform)
@@ -1669,7 +1685,7 @@ struct PathShader {
                 if (ENV && have_env() && P.emitted && (!L.hide_emitters || P.scattered)) {
                     const MtsgCamera &cam = S.cam;
                     f3 rxd, ryd;
-                    if constexpr (LENS) {
+                    if (LENS && lens_ray()) {
                         // the sensor's own differentials (dsensor.h).  The aperture sample is not
                         // kept across the bounce: dimensions 2, 3 of the sample's index, drawn again
                         // (the same table words as produce()'s next2d: the same bits)
@@ -1818,6 +1834,17 @@ struct PathShader {
                                 // twosided (twosided.cpp:105-131): the nested BSDF of the side wi is on
                                 f3 qwi = P.its.wi, qwo = wo;
                                 GBsdf *qb = &bsdf;
+                                EvalPdf ep;
+                                bool combo = false;
+                                if constexpr (COMBO && KIND < 0) {
+                                    // mixturebsdf, blendbsdf, mask and twosided over them: the chain of dcombo.h
+                                    if (bsdf.type >= BSDF_TWOSIDED) {
+                                        ep = combo_eval_pdf<BSF>((GBsdf *)S.bsdfs, (GCombo *)L.combos, (glb_f32 *)S.rtrans,
+                                                                 qb, qwi, qwo, P.its.u, P.its.v);
+                                        combo = true;
+                                    }
+                                }
+                                if (!combo) {
                                 if constexpr (EXT && KIND < 0) {
                                     if (bsdf.type == BSDF_TWOSIDED) {
                                         const bool flip = !(qwi.z > 0);
@@ -1825,8 +1852,9 @@ struct PathShader {
                                         if (flip) { qwi.z = -qwi.z; qwo.z = -qwo.z; }
                                     }
                                 }
-                                const EvalPdf ep = bsdf_eval_pdf_k<BSF, KIND>(*qb, (glb_f32 *)S.rtrans, qwi, qwo,
-                                                                              P.its.u, P.its.v, rpPre(qb, qwi));
+                                ep = bsdf_eval_pdf_k<BSF, KIND>(*qb, (glb_f32 *)S.rtrans, qwi, qwo, P.its.u, P.its.v,
+                                                                rpPre(qb, qwi));
+                                }
                                 const f3 bsdfVal = ep.val;
                                 if (!is_zero(bsdfVal) && (NOSTRICT || !L.strict_normals || dot(P.its.geoN, dd) * wo.z > 0)) {
                                     // bsdfPdf = 0 for an emitter that is not on a surface (path.cpp:192-197)
@@ -1860,7 +1888,11 @@ struct PathShader {
                     if (KIND >= 0 ? KIND == BSDF_ROUGHDIELECTRIC : bsdf.type == BSDF_ROUGHDIELECTRIC)
                         u1d = next1d(SC, smp);   // roughdielectric.cpp:554
                     BSample bs;
-                    if (EXT && KIND < 0 && bsdf.type == BSDF_TWOSIDED) {
+                    if (COMBO && KIND < 0 && bsdf.type >= BSDF_TWOSIDED) {
+                        if constexpr (COMBO)
+                            bs = combo_sample<BSF>((GBsdf *)S.bsdfs, (GCombo *)L.combos, (glb_f32 *)S.rtrans, &bsdf,
+                                                   P.its.wi, bx2, by2, P.its.u, P.its.v);
+                    } else if (EXT && KIND < 0 && bsdf.type == BSDF_TWOSIDED) {
                         // TwoSidedBRDF::sample(bRec, pdf, sample) (twosided.cpp:151-172)
                         const bool flip = P.its.wi.z < 0;
                         f3 qwi = P.its.wi;

@@ -14,7 +14,7 @@
 typedef void (*PathKernelFn)(MtsgLaunch);
 hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool stats, hipStream_t stream);
 int mtsg_path_kernel_occupancy(const MtsgLaunch &L, int *blocksPerCU);
-int mtsg_path_features(const MtsgLaunch &L);   // the scene's MTSG_FEAT_ENV | EXT | ANA bits, or MTSG_FEAT_SET_DELTA / _LENS
+int mtsg_path_features(const MtsgLaunch &L);   // the scene's MTSG_FEAT_ENV | EXT | ANA bits, or MTSG_FEAT_SET_DELTA / _LENS / _COMBO
 int mtsg_path_variant(const MtsgLaunch &L);    // the FEAT template argument mtsg_launch_path runs
 size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // dynamic LDS of the megakernel, direct_kernel and field_kernel
 bool mtsg_path_start_queue(const MtsgLaunch &L);   // the launch starts its paths from the LDS queue (dpath.h mtsg_start_queue)
@@ -23,6 +23,7 @@ bool mtsg_path_start_queue(const MtsgLaunch &L);   // the launch starts its path
 MTSG_PATH_F_DECL(0) MTSG_PATH_F_DECL(1) MTSG_PATH_F_DECL(2) MTSG_PATH_F_DECL(3) MTSG_PATH_F_DECL(6) MTSG_PATH_F_DECL(7)
 MTSG_PATH_F_DECL(1031)   // MTSG_FEAT_SET_DELTA: scenes with delta emitters
 MTSG_PATH_F_DECL(3079)   // MTSG_FEAT_SET_LENS: scenes whose sensor is not `perspective`
+MTSG_PATH_F_DECL(7175)   // MTSG_FEAT_SET_COMBO: scenes with a mixturebsdf, blendbsdf or mask
 #undef MTSG_PATH_F_DECL
 hipError_t mtsg_launch_gather(const MtsgLaunch &L, hipStream_t stream);
 hipError_t mtsg_launch_reduce(const MtsgLaunch &L, hipStream_t stream);
@@ -72,6 +73,6 @@ uint32_t mtsg_launch_bytes_wf_kernel();
 uint32_t mtsg_launch_bytes_field_kernel();
 #define MTSG_BYTES_DECL(N) uint32_t mtsg_launch_bytes_path_f##N(); uint32_t mtsg_launch_bytes_wf_shade_f##N();
 MTSG_BYTES_DECL(0) MTSG_BYTES_DECL(1) MTSG_BYTES_DECL(2) MTSG_BYTES_DECL(3) MTSG_BYTES_DECL(6) MTSG_BYTES_DECL(7)
-MTSG_BYTES_DECL(1031) MTSG_BYTES_DECL(3079)
+MTSG_BYTES_DECL(1031) MTSG_BYTES_DECL(3079) MTSG_BYTES_DECL(7175)
 #undef MTSG_BYTES_DECL
 }

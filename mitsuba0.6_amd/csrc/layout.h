@@ -69,7 +69,10 @@ struct MtsgTri {             // 48 B
 enum {
     MTSG_F_NULL = 0x00001, MTSG_F_DIFF_REFL = 0x00002, MTSG_F_DIFF_TRANS = 0x00004,
     MTSG_F_GLOSSY_REFL = 0x00008, MTSG_F_GLOSSY_TRANS = 0x00010, MTSG_F_DELTA_REFL = 0x00020,
-    MTSG_F_DELTA_TRANS = 0x00040, MTSG_F_FRONT = 0x01000, MTSG_F_BACK = 0x02000
+    MTSG_F_DELTA_TRANS = 0x00040, MTSG_F_FRONT = 0x01000, MTSG_F_BACK = 0x02000,
+    // BSDF::ESpatiallyVarying: set by a mask whose opacity is a texture (mask.cpp:98-106; host side:
+    // no kernel reads it; the leaves' records, pinned by the scene digest, do not carry it)
+    MTSG_F_SPATIALLY_VARYING = 0x04000
 };
 #define MTSG_F_SMOOTH (MTSG_F_DIFF_REFL | MTSG_F_DIFF_TRANS | MTSG_F_GLOSSY_REFL | MTSG_F_GLOSSY_TRANS)
 #define MTSG_F_TRANSMISSION (MTSG_F_DIFF_TRANS | MTSG_F_GLOSSY_TRANS | MTSG_F_DELTA_TRANS | MTSG_F_NULL)
@@ -101,7 +104,24 @@ struct MtsgBsdf {            // configured BSDF (after ctor + configure)
     // plastic (plastic.cpp:186-216): m_fdrInt, m_fdrExt (fresnelDiffuseReflectance)
     float fdr_int, fdr_ext;
     // twosided (twosided.cpp): record indices of the front / back nested BSDFs
+    // (mixturebsdf, blendbsdf, mask: nested[0] is the record's index into the side table
+    //  MtsgLaunch::combos, nested[1] = -1)
     int32_t nested[2];
+};
+
+// The combinator BSDFs' own data (mixturebsdf.cpp, blendbsdf.cpp, mask.cpp), a side table next to
+// the MtsgBsdf records (MtsgLaunch::combos; read from HBM by every engine, the LDS-resident scene
+// included): a combinator's record points here through nested[0], `child` points back at records.
+// The supported chain is [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf (dcombo.h)
+#define MTSG_COMBO_MAX 8
+struct MtsgCombo {
+    int32_t type;                    // MTSGPU_BSDF_MIXTURE / _BLEND / _MASK
+    int32_t n;                       // children: mixture 1..8, blend 2, mask 1
+    int32_t child[MTSG_COMBO_MAX];   // their BSDF records
+    float w[MTSG_COMBO_MAX];         // mixture: m_weights after configure()'s rescale
+    float cdf[MTSG_COMBO_MAX + 1];   // mixture: m_pdf's CDF (pmf.h append + normalize); m_pdf[i] = cdf[i + 1] - cdf[i]
+    float value[3];                  // blend: the constant 'weight' (x3); mask: 'opacity' after ensureEnergyConservation
+    MtsgTex tex;                     // blend 'weight' / mask 'opacity' texture (type 0: `value`)
 };
 
 enum { MTSG_EMITTER_AREA = 0, MTSG_EMITTER_ENVMAP = 1, MTSG_EMITTER_CONSTANT = 2,
@@ -123,9 +143,14 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        // the sensor is not `perspective` (dsensor.h): primary rays have their own origin, and maybe
        // an aperture draw.  Such scenes run one feature set of their own that holds everything,
        // ENV | EXT | ANA | DELTA | LENS; the sensor type is a run-time field (MtsgCameraLens) there
-       MTSG_FEAT_LENS = 2048 };
+       MTSG_FEAT_LENS = 2048,
+       // the scene holds a mixturebsdf, blendbsdf or mask (dcombo.h).  Such scenes run one feature set
+       // of their own again, the lens set | COMBO: the sensor type (`perspective` too), the delta
+       // emitters and the environment are run-time questions there
+       MTSG_FEAT_COMBO = 4096 };
 #define MTSG_FEAT_SET_DELTA (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA | MTSG_FEAT_DELTA)   // = 1031
 #define MTSG_FEAT_SET_LENS (MTSG_FEAT_SET_DELTA | MTSG_FEAT_LENS)                               // = 3079
+#define MTSG_FEAT_SET_COMBO (MTSG_FEAT_SET_LENS | MTSG_FEAT_COMBO)                              // = 7175
 enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_DIRECT = 1, MTSG_INTEGRATOR_VOLPATH = 2 };   // = MTSGPU_INTEGRATOR_*
 enum { MTSG_SAMPLER_SOBOL = 0, MTSG_SAMPLER_INDEPENDENT = 1, MTSG_SAMPLER_SFMT_REPLAY = 2,
        MTSG_SAMPLER_SFMT_BLOCKS = 3 };    // = MTSGPU_SAMPLER_*
@@ -393,6 +418,9 @@ struct MtsgLaunch {
     uint32_t lens;                         // kernel variant: the sensor is not `perspective` (the MTSG_FEAT_SET_LENS
                                            // kernels; host side only, like `delta`)
     MtsgCameraLens cam_lens;               // the camera's sensor type, aperture and focus plane (those kernels only)
+    uint32_t combo;                        // kernel variant: a mixturebsdf / blendbsdf / mask in the scene (the
+                                           // MTSG_FEAT_SET_COMBO kernels; host side only, like `delta`)
+    const MtsgCombo *combos;               // the combinators' side table (those kernels only), or null
 };
 
 // The field pass (field_kernel.hip; FieldIntegrator::Li, integrators/misc/field.cpp:124-177):

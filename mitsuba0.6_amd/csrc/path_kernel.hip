@@ -83,20 +83,30 @@ __device__ __forceinline__ f3 env_sensor(const MtsgLaunch &L, float sx, float sy
 // (integrator.cpp:171-172, before Li), the sensor's ray and its own differentials
 template <bool LENS> struct DirectAperture {};
 template <> struct DirectAperture<true> { float x, y; };
-template <bool LENS>
+// (COMBO: the combinator set holds the lens set's code and asks the sensor at run time)
+template <bool LENS, bool COMBO = false>
 __device__ __forceinline__ void direct_primary(const MtsgLaunch &L, const SobolCtx &SC, SamplerState &smp, int px, int py,
                                                float sx, float sy, DirectAperture<LENS> &ap, f3 &ro, f3 &rd, float &mint,
                                                float &maxt) {
     if constexpr (LENS) {
         ap.x = ap.y = 0.5f;
+        if constexpr (COMBO) {
+            if (L.cam_lens.type == MTSG_SENSOR_PERSPECTIVE) {
+                camera_ray(L.scene.cam, sx, sy, ro, rd, mint, maxt);
+                return;
+            }
+        }
         if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ap.x, ap.y);
         sensor_ray(L.scene.cam, L.cam_lens, sx, sy, ap.x, ap.y, ro, rd, mint, maxt);
     } else {
         camera_ray(L.scene.cam, sx, sy, ro, rd, mint, maxt);
     }
 }
-template <bool LENS>
+template <bool LENS, bool COMBO = false>
 __device__ __forceinline__ f3 direct_env_miss(const MtsgLaunch &L, float sx, float sy, const DirectAperture<LENS> &ap, f3 rd) {
+    if constexpr (COMBO) {
+        if (L.cam_lens.type == MTSG_SENSOR_PERSPECTIVE) return env_camera(L, sx, sy, rd);
+    }
     if constexpr (LENS) return env_sensor(L, sx, sy, ap.x, ap.y, rd);
     else return env_camera(L, sx, sy, rd);
 }
@@ -220,6 +230,9 @@ __device__ __forceinline__ BSample bsdf_sample_2s(const MtsgDeviceScene &S, GBsd
         rp_pre_for<(EXT ? (int)MTSG_FEAT_EXT : 0)>(bsdf, (glb_f32 *)S.rtrans, h.wi, h.u, h.v));
 }
 
+// the same through the combinators' chain (dcombo.h; the MTSG_FEAT_SET_COMBO instantiations)
+__device__ __forceinline__ bool direct_is_combo(GBsdf &bsdf) { return bsdf.type >= BSDF_TWOSIDED; }
+
 // direct_kernel's shadow rays: the any-hit traversal.  Inlined into
 // direct_kernel's nested divergent loops at -O3, hipcc (ROCm 7.2, gfx950)
 // produced wrong occlusion answers for 15% of the samples of the analytic-shape
@@ -244,7 +257,8 @@ template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLaunch L) {
     constexpr bool ENV = (FEAT & MTSG_FEAT_ENV) != 0, EXT = (FEAT & MTSG_FEAT_EXT) != 0,
                    ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0,
-                   LENS = (FEAT & MTSG_FEAT_LENS) != 0;   // the sensor's own ray (dsensor.h)
+                   LENS = (FEAT & MTSG_FEAT_LENS) != 0,   // the sensor's own ray (dsensor.h)
+                   COMBO = (FEAT & MTSG_FEAT_COMBO) != 0; // mixturebsdf / blendbsdf / mask (dcombo.h)
     extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     // the delta-emitter feature set is compiled with ENV; its scenes need not have an environment
@@ -320,13 +334,13 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
         f3 ro, rd;
         float rmint, rmaxt;
         DirectAperture<LENS> ap;
-        direct_primary<LENS>(L, SC, smp, px, py, sx, sy, ap, ro, rd, rmint, rmaxt);
+        direct_primary<LENS, COMBO>(L, SC, smp, px, py, sx, sy, ap, ro, rd, rmint, rmaxt);
         f3 Li = mk(0, 0, 0);
         Hit its;
         const bool hit = closest(ro, rd, rmint, rmaxt, its);
         const float alpha = L.has_alpha ? (hit ? 1.0f : 0.0f) : 1.0f;
         if (!hit) {
-            if (ENV && haveEnv && !L.hide_emitters) Li = direct_env_miss<LENS>(L, sx, sy, ap, rd);
+            if (ENV && haveEnv && !L.hide_emitters) Li = direct_env_miss<LENS, COMBO>(L, sx, sy, ap, rd);
         } else {
             auto &sh = hs.shapes[its.shape];
             GBsdf &bsdf = ((GBsdf *)S.bsdfs)[sh.bsdf];
@@ -349,7 +363,18 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                             const f3 wo = to_local(its.sh, ns.d);
                             f3 bsdfVal;
                             float bsdfPdf;
-                            bsdf_eval_pdf_2s<EXT>(S, bsdf, its, wo, bsdfVal, &bsdfPdf);
+                            bool combo = false;
+                            if constexpr (COMBO) {
+                                if (direct_is_combo(bsdf)) {
+                                    const EvalPdf ep = combo_eval_pdf<MTSG_FEAT_EXT>((GBsdf *)S.bsdfs, (GCombo *)L.combos,
+                                                                                     (glb_f32 *)S.rtrans, &bsdf, its.wi, wo,
+                                                                                     its.u, its.v);
+                                    bsdfVal = ep.val;
+                                    bsdfPdf = ep.pdf;
+                                    combo = true;
+                                }
+                            }
+                            if (!combo) bsdf_eval_pdf_2s<EXT>(S, bsdf, its, wo, bsdfVal, &bsdfPdf);
                             if (!is_zero(bsdfVal) && (!L.strict_normals || dot(its.geoN, ns.d) * wo.z > 0)) {
                                 if (DELTA && ns.delta) bsdfPdf = 0.0f;   // emitter->isOnSurface() ? bsdf->pdf(bRec) : 0
                                 const float pa = ns.pdf * L.frac_lum, pb = bsdfPdf * L.frac_bsdf;
@@ -368,7 +393,14 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                                       L.bsdf_dim, bx, by);
                     float u1d = 0.0f;
                     if (bsdf.type == BSDF_ROUGHDIELECTRIC) u1d = next1d_a(SC, smp, L.array_end);
-                    const BSample bs = bsdf_sample_2s<EXT>(S, bsdf, its, bx, by, u1d);
+                    BSample bs;
+                    if (COMBO && direct_is_combo(bsdf)) {
+                        if constexpr (COMBO)
+                            bs = combo_sample<MTSG_FEAT_EXT>((GBsdf *)S.bsdfs, (GCombo *)L.combos, (glb_f32 *)S.rtrans, &bsdf,
+                                                             its.wi, bx, by, its.u, its.v);
+                    } else {
+                        bs = bsdf_sample_2s<EXT>(S, bsdf, its, bx, by, u1d);
+                    }
                     if (is_zero(bs.weight)) continue;
                     const f3 wo = to_world(its.sh, bs.wo);
                     if (L.strict_normals && dot(its.geoN, wo) * bs.wo.z <= 0) continue;
@@ -739,9 +771,10 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
 }
 
 // (the MTSG_FEAT_LENS kernels are built without the queue: dmega.h QUEUE)
-bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L) && !L.lens; }
+bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L) && !L.lens && !L.combo; }
 
 int mtsg_path_features(const MtsgLaunch &L) {
+    if (L.combo) return MTSG_FEAT_SET_COMBO;   // mixturebsdf / blendbsdf / mask: the one set that holds everything
     if (L.lens) return MTSG_FEAT_SET_LENS;     // thinlens / orthographic / telecentric: the one set that holds everything
     if (L.delta) return MTSG_FEAT_SET_DELTA;   // delta-emitter scenes: the one set that holds everything
     return (L.scene.env_emitter >= 0 ? MTSG_FEAT_ENV : 0) | ((L.ext || L.ana) ? MTSG_FEAT_EXT : 0) |
@@ -753,7 +786,7 @@ int mtsg_path_features(const MtsgLaunch &L) {
 // (render_plan.cpp plan_render, L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
 // small scenes staged in LDS and the direct integrator take the generic kernel.
 static int spec_bits(const MtsgLaunch &L) {
-    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta || L.lens) return 0;   // (delta, lens: the generic set only)
+    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta || L.lens || L.combo) return 0;   // (delta, lens, combo: the generic set only)
     const int b = ((L.bset & MTSG_FEAT_GGX) ? 1 : 0) | ((L.bset & MTSG_FEAT_NORD) ? 2 : 0) | ((L.bset & MTSG_FEAT_NORC) ? 4 : 0);
     return b | ((b && (L.bset & MTSG_FEAT_NOREFN) && (mtsg_path_features(L) & MTSG_FEAT_ENV)) ? 8 : 0);
 }
@@ -770,6 +803,7 @@ static PathKernelFn path_pick(const MtsgLaunch &L, bool instr) {
         case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_pick_f6(L, bits, instr);
         case MTSG_FEAT_SET_DELTA: return mtsg_path_pick_f1031(L, bits, instr);
         case MTSG_FEAT_SET_LENS: return mtsg_path_pick_f3079(L, bits, instr);
+        case MTSG_FEAT_SET_COMBO: return mtsg_path_pick_f7175(L, bits, instr);
         default: return mtsg_path_pick_f7(L, bits, instr);
     }
 }
@@ -792,6 +826,7 @@ hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool st
             case MTSG_FEAT_EXT | MTSG_FEAT_ANA: launch_direct<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
             case MTSG_FEAT_SET_DELTA: launch_direct<MTSG_FEAT_SET_DELTA>(L, grid, stream); break;
             case MTSG_FEAT_SET_LENS: launch_direct<MTSG_FEAT_SET_LENS>(L, grid, stream); break;
+            case MTSG_FEAT_SET_COMBO: launch_direct<MTSG_FEAT_SET_COMBO>(L, grid, stream); break;
             default: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
         }
         return hipGetLastError();

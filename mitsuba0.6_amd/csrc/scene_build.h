@@ -56,6 +56,9 @@ struct HostScene {
     std::vector<float> rtrans, texcoords;
     bool ext = false;   // roughplastic or textured BSDFs: the MTSG_FEAT_EXT kernel variant
     std::vector<MtsgAnalytic> analytic;   // rectangle / disk / sphere records (MTSG_FEAT_ANA variant)
+    // mixturebsdf / blendbsdf / mask records (MtsgBsdf::nested[0] indexes them; MtsgLaunch::combos).
+    // Not empty: the MTSG_FEAT_SET_COMBO kernels.  (Not one of mtsgpu_scene_digest_host's members.)
+    std::vector<MtsgCombo> combos;
     // launch constants of the scene, formed where it is uploaded (render_plan.cpp scene_scan_n, scene_one_emitter)
     struct {
         uint32_t scan_n[6];     // as MtsgLaunch::scan_n: records | plane pairs << 16

@@ -8,7 +8,7 @@
 
 #define MTSG_WF_PICK_DECL(N) WfShadeFn mtsg_wf_pick_##N(int wk, bool instr, bool ggx);
 MTSG_WF_PICK_DECL(0) MTSG_WF_PICK_DECL(1) MTSG_WF_PICK_DECL(2) MTSG_WF_PICK_DECL(3) MTSG_WF_PICK_DECL(6)
-MTSG_WF_PICK_DECL(7) MTSG_WF_PICK_DECL(1031) MTSG_WF_PICK_DECL(3079)
+MTSG_WF_PICK_DECL(7) MTSG_WF_PICK_DECL(1031) MTSG_WF_PICK_DECL(3079) MTSG_WF_PICK_DECL(7175)
 #undef MTSG_WF_PICK_DECL
 
 // the per-block partial counters of a chunk -> MtsgLaunch::counters
@@ -50,6 +50,7 @@ static WfShadeFn wf_shade_pick(const MtsgLaunch &L, int wk, bool instr, bool ggx
         case 6: return mtsg_wf_pick_6(wk, instr, ggx);
         case MTSG_FEAT_SET_DELTA: return mtsg_wf_pick_1031(wk, instr, ggx);
         case MTSG_FEAT_SET_LENS: return mtsg_wf_pick_3079(wk, instr, ggx);
+        case MTSG_FEAT_SET_COMBO: return mtsg_wf_pick_7175(wk, instr, ggx);
         default: return mtsg_wf_pick_7(wk, instr, ggx);
     }
 }

@@ -34,7 +34,7 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
            'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
            'mtsgpu_face_normals_host', 'mtsgpu_render_fields', 'mtsgpu_render_fields_device', 'mtsgpu_develop_multi',
-           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_develop_ldr',
+           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_combo_host', 'mtsgpu_develop_ldr',
            'mtsgpu_develop_ldr_device', 'mtsgpu_plan_host']
 
 _lib = None
@@ -155,6 +155,27 @@ def albedo_factors_host(scene):
     return out[:d.num_bsdfs]
 
 
+def combo_host(scene, index):
+    """What configure() derives for the mixturebsdf / blendbsdf / mask at `index` of
+    scene.flat_bsdfs(), on the host without a device (mtsgpu_combo_host): {'n', 'weights' (the
+    mixture's m_weights after the rescale), 'cdf' (m_pdf's, n + 1 entries), 'pdf' (m_pdf[i]),
+    'value' (blend weight x3 / mask opacity), 'flags'}."""
+    L = load_library()
+    L.mtsgpu_combo_host.argtypes = [C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                    C.c_char_p, C.c_size_t]
+    d = scene.desc()
+    out = np.zeros(21, np.float32)
+    flags = C.c_int32(0)
+    buf = C.create_string_buffer(512)
+    rc = L.mtsgpu_combo_host(C.byref(d), index, abi.fptr(out), C.byref(flags), buf, 512)
+    if rc != 0:
+        raise MtsgpuError(rc, buf.value.decode())
+    n = int(out[0])
+    cdf = out[9:10 + n].copy()
+    return {'n': n, 'weights': out[1:1 + n].copy(), 'cdf': cdf, 'pdf': cdf[1:] - cdf[:-1], 'value': out[18:21].copy(),
+            'flags': flags.value}
+
+
 KD_KEYS = ('nodes', 'indices', 'inner', 'leaves', 'nonempty_leaves', 'retracted', 'pruned', 'max_depth')
 
 
@@ -250,6 +271,9 @@ PLAN_ENGINES = ('megakernel', 'wavefront', 'fields')
 VARIANT_DELTA = 1 << 18
 # ... and the instantiations of scenes whose sensor is not `perspective` (MTSG_FEAT_SET_LENS, the field pass's too)
 VARIANT_LENS = 1 << 19
+# ... and the instantiations of scenes with a mixturebsdf, blendbsdf or mask (MTSG_FEAT_SET_COMBO = 7175; they hold the
+# lens and delta code too, bits 18 and 19 then say what the scene has)
+VARIANT_COMBO = 1 << 20
 
 
 def kernel_variant_of(word):
@@ -260,11 +284,12 @@ def kernel_variant_of(word):
     if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
         return None
     feat = ((c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0) |
-            (1024 if c & (VARIANT_DELTA | VARIANT_LENS) else 0) | (2048 if c & VARIANT_LENS else 0))
+            (1024 if c & (VARIANT_DELTA | VARIANT_LENS | VARIANT_COMBO) else 0) |
+            (2048 if c & (VARIANT_LENS | VARIANT_COMBO) else 0) | (4096 if c & VARIANT_COMBO else 0))
     instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
     b = lambda v: 'true' if v else 'false'
     return {'instr': instr, 'scene_lds': lds, 'feat': feat, 'waves': waves, 'delta': bool(c & VARIANT_DELTA),
-            'lens': bool(c & VARIANT_LENS),
+            'lens': bool(c & VARIANT_LENS), 'combo': bool(c & VARIANT_COMBO),
             'name': 'path_kernel<%s, %s, %d, %d>' % (b(instr), b(lds), feat, waves)}
 
 
@@ -426,6 +451,10 @@ class Context:
         {samplePos.x, samplePos.y, alpha, hit, f0.rgb, ...} or None; stats dict)."""
         fields = [f if isinstance(f, FieldIntegrator) else FieldIntegrator(f) for f in fields]
         sc = self.scene
+        if any(f.field == 'albedo' for f in fields) and any(b.type in ('mixturebsdf', 'blendbsdf', 'mask')
+                                                            for b in sc.flat_bsdfs()[0]):
+            raise NotImplementedError("the 'albedo' field is not supported in a scene with a mixturebsdf, blendbsdf "
+                                      "or mask BSDF")
         W, H = sc.sensor.width, sc.sensor.height
         x0, y0, w, h = window if window else (integ.crop or (0, 0, W, H))
         p = integ.params(W, H, x0, y0, w, h, row[0], row[1], row[2])

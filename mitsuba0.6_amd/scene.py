@@ -66,7 +66,10 @@ def _spec(v):
 BSDF_TYPES = {'diffuse': abi.BSDF_DIFFUSE, 'roughconductor': abi.BSDF_ROUGHCONDUCTOR,
               'roughdielectric': abi.BSDF_ROUGHDIELECTRIC, 'roughplastic': abi.BSDF_ROUGHPLASTIC,
               'conductor': abi.BSDF_CONDUCTOR, 'dielectric': abi.BSDF_DIELECTRIC,
-              'plastic': abi.BSDF_PLASTIC, 'twosided': abi.BSDF_TWOSIDED}
+              'plastic': abi.BSDF_PLASTIC, 'twosided': abi.BSDF_TWOSIDED,
+              'mixturebsdf': abi.BSDF_MIXTURE, 'blendbsdf': abi.BSDF_BLEND, 'mask': abi.BSDF_MASK}
+# the BSDFs that hold other BSDFs in `nested`
+WRAPPERS = ('twosided', 'mixturebsdf', 'blendbsdf', 'mask')
 
 
 @dataclass
@@ -75,7 +78,13 @@ class BSDF:
     conductor / dielectric / plastic / twosided with Mitsuba property names.
     `reflectance` (diffuse), `diffuseReflectance` ((rough)plastic) and `alpha`
     (rough BSDFs, isotropic) may be a Checkerboard.  A twosided BSDF holds its
-    one or two nested BSDFs in `nested` (twosided.cpp:63-103)."""
+    one or two nested BSDFs in `nested` (twosided.cpp:63-103).
+
+    The combinators hold theirs there too: `mixturebsdf` (weights=[...], one per nested
+    BSDF, up to 8), `blendbsdf` (weight: a float or a Checkerboard; two nested) and `mask`
+    (opacity: a spectrum or a Checkerboard; one nested).  One chain is supported,
+    [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf; the library refuses the
+    rest when the scene is checked or uploaded."""
     type: str = 'diffuse'
     reflectance: object = (0.5, 0.5, 0.5)
     distribution: str = 'beckmann'
@@ -95,7 +104,10 @@ class BSDF:
     nonlinear: bool = False
     rtransDir: Optional[str] = None    # where data/microfacet/<distribution>.dat is looked up first (rtrans.py)
     ensureEnergyConservation: bool = True
-    nested: list = field(default_factory=list)   # twosided: [front] or [front, back]
+    nested: list = field(default_factory=list)   # twosided: [front] or [front, back]; the combinators' children
+    weights: Optional[list] = None     # mixturebsdf 'weights'
+    weight: object = 0.5               # blendbsdf 'weight' (blendbsdf.cpp:63)
+    opacity: object = 0.5              # mask 'opacity' (mask.cpp:76-77)
 
     def int_ior(self):
         if self.intIOR is not None:
@@ -112,6 +124,22 @@ class BSDF:
                           'phong': abi.DISTR_PHONG, 'as': abi.DISTR_PHONG}[self.distribution.lower()]
         d.sample_visible = int(self.sampleVisible)
         d.ensure_energy_conservation = int(self.ensureEnergyConservation)
+        if self.type == 'mixturebsdf':
+            w = [] if self.weights is None else [float(x) for x in self.weights]
+            if len(w) > abi.MIXTURE_MAX or len(self.nested) > abi.MIXTURE_MAX:
+                raise NotImplementedError('mixturebsdf: more than %d nested BSDFs are not supported' % abi.MIXTURE_MAX)
+            d.num_weights = len(w)
+            d.weights[:len(w)] = w
+        if self.type == 'blendbsdf':
+            if isinstance(self.weight, Checkerboard):
+                self.weight.fill(d.weight_tex)
+            else:
+                d.weight = float(self.weight)
+        if self.type == 'mask':
+            if isinstance(self.opacity, Checkerboard):
+                self.opacity.fill(d.opacity_tex)
+            else:
+                d.opacity[:] = _spec(self.opacity)
         # MicrofacetDistribution(props) defaults alphaU = alphaV = 0.1 (microfacet.h:99-101,117-130)
         if isinstance(self.alpha, Checkerboard):
             if self.alphaU is not None or self.alphaV is not None:
@@ -337,18 +365,27 @@ class Scene:
         return sum(1 if m.analytic else int(m.indices.shape[0]) for m in self.meshes)
 
     def flat_bsdfs(self):
-        """The BSDF list as desc() packs it: twosided's nested BSDFs go after the scene's own
-        (mesh indices stay valid); (list, {twosided index: [nested indices]})."""
+        """The BSDF list as desc() packs it: the nested BSDFs of twosided, mixturebsdf, blendbsdf
+        and mask go after the scene's own (mesh indices stay valid), a nested wrapper's own
+        children after those; (list, {wrapper index: [nested indices]})."""
         flat = list(self.bsdfs)
         nested_idx = {}
-        for i, b in enumerate(self.bsdfs):
-            if b.type == 'twosided':
-                if not 1 <= len(b.nested) <= 2:
+        i = 0
+        while i < len(flat):
+            b = flat[i]
+            if b.type in WRAPPERS:
+                if b.type == 'twosided' and not 1 <= len(b.nested) <= 2:
                     raise ValueError('twosided: one or two nested BSDFs (twosided.cpp:82-87, 161-170)')
+                if b.type == 'blendbsdf' and len(b.nested) != 2:
+                    raise ValueError('blendbsdf: BSDF count mismatch: expected two nested BSDF instances!')
+                if b.type == 'mask' and len(b.nested) != 1:
+                    raise ValueError('mask: A child BSDF is required' if not b.nested
+                                     else 'mask: only a single nested BSDF can be added')
                 nested_idx[i] = []
                 for nb in b.nested:
                     nested_idx[i].append(len(flat))
                     flat.append(nb)
+            i += 1
         return flat, nested_idx
 
     def desc(self):
@@ -392,7 +429,11 @@ class Scene:
         for i, b in enumerate(flat):
             bdi = b.to_desc()
             keep.append(getattr(bdi, '_keep', None))
-            if i in nested_idx:
+            if i in nested_idx and b.type == 'mixturebsdf':
+                bdi.num_children = len(nested_idx[i])
+                for k, j in enumerate(nested_idx[i][:abi.MIXTURE_MAX]):
+                    bdi.children[k] = j
+            elif i in nested_idx:
                 for k, j in enumerate(nested_idx[i]):
                     bdi.nested[k] = j
             bd[i] = bdi

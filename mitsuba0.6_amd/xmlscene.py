@@ -335,10 +335,58 @@ class XMLSceneLoader:
                 raise SceneError('A nested one-sided material is required!')
             if len(nested) > 2:
                 raise SceneError('No more than two nested BRDFs can be added!')
+            for nb in nested:
+                if nb.type in ('twosided', 'mask'):
+                    raise NotImplementedError('twosided: a nested "%s" BSDF is not on the GPU path' % nb.type)
             return BSDF('twosided', nested=nested)
+        if t in ('mixturebsdf', 'blendbsdf', 'mask'):
+            # mixturebsdf.cpp:67-98, 279-287; blendbsdf.cpp:60-75, 272-284; mask.cpp:74-78, 225-237 (addChild).
+            # The GPU path walks one chain: [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf
+            tex = self._tex_params(p, {'mixturebsdf': (), 'blendbsdf': ('weight',), 'mask': ('opacity',)}[t])
+            nested = [self.make_bsdf(c) for _, c in p.children if c.tag == 'bsdf']
+            for _, c in p.children:
+                if c.tag not in ('bsdf', 'texture'):
+                    raise SceneError('%s: unexpected <%s> child' % (t, c.tag))
+            for nb in nested:
+                if nb.type == 'mask' or (t != 'mask' and nb.type in ('twosided', 'mixturebsdf', 'blendbsdf')):
+                    raise NotImplementedError('%s: a nested "%s" BSDF is not on the GPU path (the supported chain '
+                                              'is [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf)'
+                                              % (t, nb.type))
+            below = list(nested)
+            for nb in nested:
+                below += nb.nested + [x for y in nb.nested for x in y.nested]
+            if any(x.type == 'roughdielectric' for x in below):
+                raise NotImplementedError('%s: a nested "roughdielectric" BSDF is not on the GPU path' % t)
+            ens = p.get('ensureEnergyConservation', True)
+            if t == 'mixturebsdf':
+                toks = [x for x in re.split(r'[ ,;]+', str(p.get('weights', ''))) if x]
+                if not toks:
+                    raise SceneError('No weights were supplied!')
+                try:
+                    weights = [float(x) for x in toks]
+                except ValueError:
+                    raise SceneError('Could not parse the BSDF weights!')
+                if any(w < 0 for w in weights):
+                    raise SceneError('Invalid BSDF weight!')
+                if len(nested) > 8:
+                    raise NotImplementedError('mixturebsdf: more than 8 nested BSDFs are not on the GPU path')
+                if len(nested) != len(weights):
+                    raise SceneError('BSDF count mismatch: %d bsdfs, but specified %d weights' % (len(nested), len(weights)))
+                if sum(weights) <= 0:
+                    raise SceneError('The weights must sum to a value greater than zero!')
+                return BSDF('mixturebsdf', weights=weights, nested=nested, ensureEnergyConservation=ens)
+            if t == 'blendbsdf':
+                if len(nested) != 2:
+                    raise SceneError('BSDF count mismatch: expected two nested BSDF instances!')
+                return BSDF('blendbsdf', weight=tex.get('weight', float(p.get('weight', 0.5))), nested=nested,
+                            ensureEnergyConservation=ens)
+            if len(nested) != 1:
+                raise SceneError('A child BSDF is required' if not nested else 'Only a single nested BRDF can be added!')
+            return BSDF('mask', opacity=tex.get('opacity', p.get('opacity', 0.5)), nested=nested,
+                        ensureEnergyConservation=ens)
         raise NotImplementedError('BSDF plugin "%s" is not on the GPU path (diffuse, roughconductor, '
                                   'roughdielectric, roughplastic, conductor, dielectric, plastic, '
-                                  'twosided)' % t)
+                                  'twosided, mixturebsdf, blendbsdf, mask)' % t)
 
     def make_area(self, p):
         if p.plugin != 'area':
@@ -718,6 +766,17 @@ def _bsdf_xml(b, ind, bid=None):
     L = ['%s<bsdf type="%s"%s>' % (ind, b.type, ' id="%s"' % bid if bid else '')]
     i2 = ind + '  '
     if b.type == 'twosided':
+        for nb in b.nested:
+            L += _bsdf_xml(nb, i2)
+    elif b.type in ('mixturebsdf', 'blendbsdf', 'mask'):
+        if b.type == 'mixturebsdf':
+            L.append(i2 + '<string name="weights" value="%s"/>' % ', '.join(_fmt(w) for w in b.weights))
+        elif b.type == 'blendbsdf':
+            L.append(i2 + (_checker_xml('weight', b.weight) if isinstance(b.weight, Checkerboard)
+                           else '<float name="weight" value="%s"/>' % _fmt(b.weight)))
+        else:
+            L.append(i2 + _spec_xml('opacity', b.opacity))
+        L.append(i2 + '<boolean name="ensureEnergyConservation" value="%s"/>' % str(bool(b.ensureEnergyConservation)).lower())
         for nb in b.nested:
             L += _bsdf_xml(nb, i2)
     elif b.type == 'diffuse':
