@@ -377,7 +377,8 @@ struct MtsgLaunch {
                                       // degenerate k = 3 records dropped; counts per group
                                       // in the low 16 bits; the high 16: each group leads with that many pairs
                                       // of records sharing plane and vertex A (partners at 2i, 2i + 1), its
-                                      // singles follow (render_plan.cpp mtsg_scan_layout)
+                                      // singles follow (render_plan.cpp mtsg_scan_layout).  A general record
+                                      // here has +0 for a -0 n_u / n_v where its n_d != 0 (the copy only)
     uint32_t num_verts, num_shapes;   // sizes of the triangle data SCENE_LDS kernels stage in LDS
     int32_t integrator;               // MTSGPU_INTEGRATOR_*
     uint32_t sampler;                 // MTSGPU_SAMPLER_*

@@ -45,6 +45,33 @@ RenderKnobs read_knobs() {
 // n_d only, its loops never read n_u / n_v).  Bit-equality is an equivalence,
 // so pairing each record with the next unpaired equal one leaves at most one
 // single per plane.  MTSGPU_NO_SCAN_PAIRS: no pairs (A/B and tests).
+//
+// Canonical zero (MTSG_SCAN_ZERO_SIGN, default 1; with and without pairs): the two
+// triangles of a quad can come out of the TriAccel construction with n_u (or n_v)
+// = +0 in one and -0 in the other, which the bit-equality above keeps apart.  The
+// copy in g -- only g, the array the scans read; H.tris, the LDS and BVH records
+// and the oracle's keep theirs -- gets +0 for an n_u or n_v that is -0 wherever the
+// record's n_d is not +-0.  No reader of g (scan_pair_k; scan_k in the megakernel's
+// scan_tris, the wavefront engine, direct_kernel and trace_rays with its arbitrary
+// mint and maxt) can tell, for any ray:
+//  * numerator ((n_d - o_u n_u) - o_v n_v) - o_k: a finite o_u times +-0 is a zero,
+//    and n_d minus a zero of either sign is n_d exactly when n_d != 0 (also an
+//    infinite or NaN n_d).  A non-finite o_u makes the product NaN under both signs.
+//    (With n_d = -0 the difference is +0 or -0 by that sign, and through t = +-0, a
+//    zero origin and a zero a_u it reaches a stored t, u or v: hence the exclusion.)
+//  * denominator (d_u n_u + d_v n_v) + d_k: the zero product matters only where
+//    d_v n_v is a zero too and d_k = 0; then the denominator is a zero of one sign or
+//    the other and t is +-inf, or NaN with a zero numerator, either way.  -inf fails
+//    t < mint.  +inf passes t > maxt only against maxt = +inf, and then hu = o_u +
+//    t d_u - a_u and hv are each infinite or NaN, so are u and v (inf * 0 = NaN), and
+//    u >= 0, v >= 0, u + v <= 1 cannot all hold.  A NaN t passes the interval test
+//    and fails u >= 0 the same way.  So a ray that sees the sign is rejected under
+//    both, and no accept decision and no stored (t, u, v) changes.
+// The same holds with u and v exchanged (n_v = -0).  The aligned groups' records, whose
+// partners need not share n_u / n_v and whose loops never read them, are copied as they are.
+#ifndef MTSG_SCAN_ZERO_SIGN
+#define MTSG_SCAN_ZERO_SIGN 1
+#endif
 void mtsg_scan_layout(const std::vector<MtsgTri> &tris, std::vector<MtsgTri> &g, uint32_t n[6], uint32_t np[6]) {
     const bool pairs = !std::getenv("MTSGPU_NO_SCAN_PAIRS");
     auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
@@ -53,7 +80,13 @@ void mtsg_scan_layout(const std::vector<MtsgTri> &tris, std::vector<MtsgTri> &g,
         for (uint32_t al = 0; al < 2; ++al) {
             std::vector<MtsgTri> m, singles;
             for (const MtsgTri &t : tris)
-                if (t.k == k && (uint32_t)(t.n_u == 0.0f && t.n_v == 0.0f) == al) m.push_back(t);
+                if (t.k == k && (uint32_t)(t.n_u == 0.0f && t.n_v == 0.0f) == al) {
+                    m.push_back(t);
+                    if (MTSG_SCAN_ZERO_SIGN && !al && t.n_d != 0.0f) {   // (t.n_d != 0: neither +0 nor -0)
+                        if (bits(t.n_u) == 0x80000000u) m.back().n_u = 0.0f;
+                        if (bits(t.n_v) == 0x80000000u) m.back().n_v = 0.0f;
+                    }
+                }
             std::vector<char> used(m.size(), 0);
             uint32_t &cnt = np[2 * k + al];
             cnt = 0;

@@ -108,6 +108,8 @@ void launch_geometry(MtsgLaunch &L, uint32_t x0, uint32_t y0, uint32_t width, ui
 inline uint32_t sobol_nibbles(uint32_t indexBits) { return indexBits <= 32 ? 8u : (uint32_t)MTSG_NIBBLES; }
 
 // Launch constants of a scene, HostScene::launch (mtsgpu_upload_scene and mtsgpu_plan_host form them)
+// g: the tiny-scene scan's copy of `tris`, grouped and paired; a copy's -0 n_u / n_v is +0 where
+// n_d != 0 (-DMTSG_SCAN_ZERO_SIGN=0: copied as they are), which no scan can tell (render_plan.cpp)
 void mtsg_scan_layout(const std::vector<MtsgTri> &tris, std::vector<MtsgTri> &g, uint32_t n[6], uint32_t np[6]);
 // the scan's grouped records `g` (empty: not a scan scene) and their packed counts
 void scene_scan_n(const HostScene &H, std::vector<MtsgTri> &g, uint32_t scan_n[6]);

@@ -73,6 +73,59 @@ __global__ __launch_bounds__(256) void valu_calib_pk(float *out, int iters, floa
     if (s == 12345.678f) out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
+// the operand form of a scan that multiplies one per-lane value by two wave-uniform
+// coefficients (OP 2): p = a.x * (s0, s1), q = a.y * (s2, s3), a = p + q -- two v_pk_mul_f32
+// whose first source is one VGPR broadcast to both halves (op_sel_hi) and whose second is an
+// SGPR pair, and one v_pk_add_f32 of VGPR pairs.  OP 3: the same with the coefficient pairs
+// held in VGPR pairs.  4 independent chains per lane
+template <int W, int OP>
+__global__ __launch_bounds__(256) void valu_calib_pk_bcast(float *out, int iters, float x, float y, float z, float w) {
+    f2 a[CHAINS / 2];
+#pragma unroll
+    for (int c = 0; c < CHAINS / 2; ++c) a[c] = f2{(float)(threadIdx.x + 2 * c), (float)(threadIdx.x + 2 * c + 1)};
+    f2 xs = {x, y}, ys = {z, w};
+    if (OP == 3) asm volatile("" : "+v"(xs), "+v"(ys));
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int c = 0; c < CHAINS / 2; ++c) {
+                const f2 p = a[c].x * xs, q = a[c].y * ys;
+                a[c] = p + q;
+            }
+        }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CHAINS / 2; ++c) s += a[c].x + a[c].y;
+    if (s == 12345.678f) out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+template <int W, int OP>
+static void run_pk_bcast(int cus, int iters, float *out) {
+    const int grid = cus * W;
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0));
+    CHECK(hipEventCreate(&e1));
+    hipLaunchKernelGGL((valu_calib_pk_bcast<W, OP>), dim3(grid), dim3(256), 0, 0, out, iters / 8, 0.4995f, 0.4996f, 0.4997f, 0.4998f);
+    CHECK(hipDeviceSynchronize());
+    CHECK(hipEventRecord(e0));
+    hipLaunchKernelGGL((valu_calib_pk_bcast<W, OP>), dim3(grid), dim3(256), 0, 0, out, iters, 0.4995f, 0.4996f, 0.4997f, 0.4998f);
+    CHECK(hipEventRecord(e1));
+    CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    const double waveInsts = (double)grid * 4 * iters * 4 * (CHAINS / 2) * 3;   // two v_pk_mul and a v_pk_add per chain and step
+    const double simds = (double)cus * 4;
+    std::printf("{\"kernel\": \"valu_calib_pk_bcast<%d, %d>\", \"op\": \"%s\", \"waves_per_simd\": %d, \"grid\": %d, "
+                "\"iters\": %d, \"kernel_ms\": %.4f, \"wave_valu_insts\": %.0f, \"wave_insts_per_simd_per_ns\": %.5f, "
+                "\"simd_cycles_per_wave_inst_at_2p4GHz\": %.4f}\n",
+                W, OP, OP == 2 ? "2 v_pk_mul_f32 (VGPR broadcast x SGPR pair) + v_pk_add_f32" : "2 v_pk_mul_f32 (VGPR broadcast x VGPR pair) + v_pk_add_f32",
+                W, grid, iters, ms, waveInsts, waveInsts / simds / (ms * 1e6), simds * 2.4e9 * (ms / 1e3) / waveInsts);
+    CHECK(hipEventDestroy(e0));
+    CHECK(hipEventDestroy(e1));
+}
+
 template <int W, int OP>
 static void run_pk(int cus, int iters, float *out) {
     const int grid = cus * W;
@@ -139,6 +192,10 @@ int main(int argc, char **argv) {
     run_pk<8, 0>(p.multiProcessorCount, iters, out);
     run_pk<4, 1>(p.multiProcessorCount, iters, out);
     run_pk<8, 1>(p.multiProcessorCount, iters, out);
+    run_pk_bcast<4, 2>(p.multiProcessorCount, iters, out);
+    run_pk_bcast<8, 2>(p.multiProcessorCount, iters, out);
+    run_pk_bcast<4, 3>(p.multiProcessorCount, iters, out);
+    run_pk_bcast<8, 3>(p.multiProcessorCount, iters, out);
     CHECK(hipFree(out));
     return 0;
 }
