@@ -32,6 +32,18 @@
 #define MTSG_HOLD_PAIR 1
 #endif
 
+// The tiny set: path_kernel<*, true, MTSG_FEAT_DIFF, 4> -- the kernel of the all-diffuse LDS scenes,
+// bench.py's C1 / C2 -- is built for the Sobol sampler with indices below 2^32 only: no
+// `independent` draw, no SFMT replay and its start loop, no 13-nibble draw.  Those are
+// launch-uniform choices, but register allocation, SGPR spilling and code size belong to the whole
+// function, so the hot loop paid for them (DESIGN.md 4 "Tiny set").  render_plan.cpp plan_render
+// sends every other launch of such a scene to the generic kernel (mtsg_tiny_set, layout.h).
+// L.scan and the loop without the queue stay run-time choices: MTSGPU_NO_SCAN launches keep
+// this kernel.  -DMTSG_TINY_SET=0 (A/B builds): the kernel with every choice at run time
+#ifndef MTSG_TINY_SET
+#define MTSG_TINY_SET 1
+#endif
+
 // diagnostic build (-DMTSG_MK_STAMPS): wave cycles per megakernel section,
 // summed into counters 11-14 (start, shadow trace, closest trace, shade) by
 // lane 0 of each wave.  s_memtime without draining the memory counters: a
@@ -92,6 +104,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     // interval longer, and the aperture draw would run beside every lane's live path state;
     // mtsg_path_start_queue says the same of their launches.  They start as the kernels
     // without the queue do, holding a pair's first splat record)
+    constexpr bool TINY = MTSG_TINY_SET && SCENE_LDS && (FEAT & MTSG_FEAT_DIFF) != 0 && WAVES == 4;
     constexpr bool QUEUE = SCENE_LDS && MTSG_START_QUEUE && (FEAT & MTSG_FEAT_LENS) == 0;
     // a production pass retires the samples whose camera ray misses the scene: without an
     // environment emitter their record is known once the ray exists
@@ -103,7 +116,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     PathState st;
     st.active = false;
     st.pix = 0;
-    if (!L.replay) mtsg_run_init(L, g, round, st.pix);   // the lane's one division
+    if (TINY || !L.replay) mtsg_run_init(L, g, round, st.pix);   // the lane's one division
     uint32_t prodPix = st.pix;
     uint32_t qHead = 0, qCount = 0, qPasses = 0;   // wave-uniform: the batch's unread entries, production passes
     uint32_t qRetired = 0;                         // wave-uniform: samples the passes finished themselves
@@ -123,7 +136,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
         // C4 +3.8%, C5 +0.7%, C3 0 (profiles/r04_ab_fresh_view.log)
         const MtsgLaunch &L = launch_fresh();
         const MtsgDeviceScene &S = L.scene;
-        const LdsView<SCENE_LDS> V = lds_view<SCENE_LDS>(L, lds);
+        LdsView<SCENE_LDS> V = lds_view<SCENE_LDS>(L, lds);
+        if constexpr (TINY) {   // what mtsg_tiny_set(L) says of every launch of this kernel, as constants
+            V.SC.indep = false;
+            V.SC.replay = false;
+            V.SC.nibbles = 8;
+        }
         lds_node *ldsNodes = V.nodes;
         lds_tri *ldsTris = V.tris;
         lds_stk_n *stkN = (lds_stk_n *)(lds + V.stackBase) + threadIdx.x;
@@ -235,7 +253,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
             if (!__any(st.active)) break;
         } else {
         while (!st.active && !done) {
-            if (L.replay) {   // SFMT replay: this lane's unit, pixel after pixel, in order
+            if (!TINY && L.replay) {   // SFMT replay: this lane's unit, pixel after pixel, in order
                 const uint32_t unit = blockIdx.x * BLOCK + threadIdx.x;
                 if (unit >= L.units) { done = true; break; }
                 const uint32_t k0 = L.unit_start[unit], n = L.unit_start[unit + 1] - k0;

@@ -1500,7 +1500,7 @@ struct PathShader {
         if (SC.indep)
             smp.sobolIndex = indep_key((uint32_t)px, (uint32_t)py, j);
         else if (L.lut.m > 1)
-            smp.sobolIndex = sobol_lookup_lds(L.lut, ycolTab, L.nibbles, j, (uint32_t)px, (uint32_t)py, L.scramble64);
+            smp.sobolIndex = sobol_lookup_lds(L.lut, ycolTab, SC.nibbles, j, (uint32_t)px, (uint32_t)py, L.scramble64);
         else
             smp.sobolIndex = j;
         float u, v;

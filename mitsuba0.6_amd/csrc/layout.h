@@ -363,7 +363,8 @@ struct MtsgLaunch {
     uint32_t waves;                   // kernel variant: waves per SIMD it is compiled for (3 or 4)
     uint32_t ext;                     // kernel variant: roughplastic / textured BSDFs present
     uint32_t ana;                     // kernel variant: analytic shapes present (implies ext)
-    uint32_t all_diffuse;             // kernel variant: every BSDF is diffuse (MTSG_FEAT_DIFF)
+    uint32_t all_diffuse;             // kernel variant: every BSDF is diffuse (MTSG_FEAT_DIFF); an LDS scene's
+                                      // megakernel launch: and mtsg_tiny_set holds (render_plan.cpp)
     uint32_t bset;                    // the scene's MTSG_FEAT_GGX / NORD / NORC bits (render_plan.cpp plan_bset)
     uint32_t delta;                   // kernel variant: delta emitters present (the MTSG_FEAT_SET_DELTA kernels)
     uint32_t xcds;                    // XCDs the device's CUs span (workgroup -> XCD remap; 1: none)
@@ -459,6 +460,13 @@ struct MtsgFieldArgs {
 #else
 #define MTSG_HD inline
 #endif
+
+// The launches the tiny-set megakernel path_kernel<*, true, MTSG_FEAT_DIFF, 4> is built for (dmega.h
+// TINY holds these as constants): the Sobol sampler -- not `independent`, not an SFMT replay --
+// with sample indices below 2^32 (8 nibbles).  render_plan.cpp plan_render routes by it
+MTSG_HD bool mtsg_tiny_set(const MtsgLaunch &L) {
+    return L.sampler == MTSG_SAMPLER_SOBOL && !L.replay && L.nibbles == 8;
+}
 
 // n / d and n % d by rcp = floor(2^32 / d) (2^32 - 1 for d = 1), exact for every 32-bit n
 // and every d >= 1: n * rcp / 2^32 lies in (n / d - 1, n / d], so its floor is the quotient

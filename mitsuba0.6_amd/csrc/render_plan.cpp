@@ -20,6 +20,7 @@ RenderKnobs read_knobs() {
     K.no_scene_lds = std::getenv("MTSGPU_NO_SCENE_LDS") != nullptr;
     K.no_scan = std::getenv("MTSGPU_NO_SCAN") != nullptr;
     K.no_diff_variant = std::getenv("MTSGPU_NO_DIFF_VARIANT") != nullptr;
+    K.no_tiny_set = std::getenv("MTSGPU_NO_TINY_SET") != nullptr;
     K.no_bsdf_sets = std::getenv("MTSGPU_NO_BSDF_SETS") != nullptr;
     K.no_refn_spec = std::getenv("MTSGPU_NO_REFN_SPEC") != nullptr;
     K.waves = (e = std::getenv("MTSGPU_WAVES")) ? (std::atoi(e) == 4 ? 4u : 3u) : 0u;
@@ -252,6 +253,20 @@ void plan_variant(MtsgLaunch &L, const HostScene &H, const mtsgpu_render_params 
     if (K.sobol_lds_dims >= 0) L.lds_dims = (uint32_t)K.sobol_lds_dims;
 }
 
+// The tiny set (dmega.h TINY): the all-diffuse LDS kernel at 4 waves/SIMD holds the Sobol sampler
+// with 8-nibble indices alone.  A megakernel launch of such a scene outside that set (layout.h
+// mtsg_tiny_set: the independent sampler, an SFMT replay, a sample index of 2^32 or more), or any
+// under MTSGPU_NO_TINY_SET, takes the generic LDS kernel path_kernel<*, true, 0, 3>, which renders
+// the same samples with every choice at run time.  (direct_kernel, the wavefront engine and the
+// field pass do not run the megakernel: their plan is as it was.  MTSGPU_NO_SCAN launches stay:
+// the kernel keeps the BVH traversal and the loop without the queue as run-time choices)
+void plan_tiny_set(MtsgLaunch &L, bool megakernel, const RenderKnobs &K) {
+    if (!megakernel || !L.scene_lds || !L.all_diffuse) return;
+    if (mtsg_tiny_set(L) && !K.no_tiny_set) return;
+    L.all_diffuse = 0;
+    L.waves = K.waves ? K.waves : 3;
+}
+
 // MIDirectIntegrator::configure / configureSampler (direct.cpp:128-143)
 void plan_direct(MtsgLaunch &L, const mtsgpu_render_params &P) {
     const uint32_t nl = P.emitter_samples, nb = P.bsdf_samples;
@@ -417,7 +432,9 @@ int plan_render(const HostScene &H, const mtsgpu_render_params &Pr, uint32_t num
                       ? (P->width + MTSG_BLOCK_SIZE - 1) / MTSG_BLOCK_SIZE * ((P->height + MTSG_BLOCK_SIZE - 1) / MTSG_BLOCK_SIZE)
                       : 1u;
     }
-    return plan_engine(*P, FJ, pathLike, replay, K, plan, err);
+    if (int rc = plan_engine(*P, FJ, pathLike, replay, K, plan, err)) return rc;
+    plan_tiny_set(L, plan.engine == MTSG_ENGINE_MEGAKERNEL && pathLike, K);
+    return MTSGPU_OK;
 }
 
 LaunchPlan plan_launch(const RenderPlan &plan, uint32_t j0, int blocks_per_cu) {

@@ -27,6 +27,8 @@ struct RenderKnobs {
     bool no_scene_lds;            // MTSGPU_NO_SCENE_LDS: small scenes are not staged in LDS
     bool no_scan;                 // MTSGPU_NO_SCAN: tiny scenes traverse their BVH (and take no start queue)
     bool no_diff_variant;         // MTSGPU_NO_DIFF_VARIANT: all-diffuse scenes take the generic kernel
+    bool no_tiny_set;             // MTSGPU_NO_TINY_SET: the all-diffuse LDS scenes' megakernel launches take the generic
+                                  // kernel, as those outside the tiny set do (A/B and tests)
     bool no_bsdf_sets;            // MTSGPU_NO_BSDF_SETS: large scenes take the generic kernel
     bool no_refn_spec;            // MTSGPU_NO_REFN_SPEC: envmap-only scenes keep refN (no MTSG_FEAT_NOREFN)
     uint32_t waves;               // MTSGPU_WAVES: 4 for "4", else 3; unset: 0 (the plan decides)
