@@ -95,8 +95,7 @@ const std::string &launch_layout_error() {
             {"path_kernel", mtsg_launch_bytes_path_kernel()}, {"wf_kernel", mtsg_launch_bytes_wf_kernel()},
             {"field_kernel", mtsg_launch_bytes_field_kernel()},
 #define MTSG_BYTES_ROW(N) {"path_f" #N, mtsg_launch_bytes_path_f##N()}, {"wf_shade_f" #N, mtsg_launch_bytes_wf_shade_f##N()},
-            MTSG_BYTES_ROW(0) MTSG_BYTES_ROW(1) MTSG_BYTES_ROW(2) MTSG_BYTES_ROW(3) MTSG_BYTES_ROW(6) MTSG_BYTES_ROW(7)
-            MTSG_BYTES_ROW(1031) MTSG_BYTES_ROW(3079) MTSG_BYTES_ROW(7175)
+            MTSG_FEAT_SETS(MTSG_BYTES_ROW)
 #undef MTSG_BYTES_ROW
         };
         for (const auto &o : objs)

@@ -16,7 +16,7 @@ bool mtsg_invert4(const float *m16, float *inv16) {
     return true;
 }
 
-// fill_hit's face normal (dpath.h; skdtree.h:355-360): cross(p1 - p0, p2 - p0) as dmath.h
+// fill_hit's face normal (dhit.h; skdtree.h:355-360): cross(p1 - p0, p2 - p0) as dmath.h
 // forms it, its length by a correctly rounded sqrt, 1 / length, three products; left
 // as it is when it is all zero.  (This unit is built with -ffp-contract=off.)
 void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n) {

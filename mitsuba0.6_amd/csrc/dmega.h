@@ -90,7 +90,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
     constexpr bool STATS = INSTR;
     constexpr bool ANA = (FEAT & MTSG_FEAT_ANA) != 0;
     constexpr bool HNODES = (FEAT & (MTSG_FEAT_GGX | MTSG_FEAT_NORD | MTSG_FEAT_NORC)) != 0;
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     (void)stage_lds<SCENE_LDS>(L, lds);
     PathCounters c = {};   // INSTR statistics only: the always-on counts are wave-uniform (wc)
     WaveCounters wc = {};
@@ -131,8 +131,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void path_kernel(MtsgLaunch L) {   //
 #endif
 
     while (true) {
-        // the launch record re-read per bounce instead of held (dpath.h launch_fresh),
-        // and the LDS / scene pointers re-derived from it (dpath.h lds_view): C2 +2.0%,
+        // the launch record re-read per bounce instead of held (dstage.h launch_fresh),
+        // and the LDS / scene pointers re-derived from it (dstage.h lds_view): C2 +2.0%,
         // C4 +3.8%, C5 +0.7%, C3 0 (profiles/r04_ab_fresh_view.log)
         const MtsgLaunch &L = launch_fresh();
         const MtsgDeviceScene &S = L.scene;

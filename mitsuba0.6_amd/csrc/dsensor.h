@@ -1,9 +1,12 @@
-// dsensor.h -- the primary ray of the projective sensors other than `perspective`
-// (src/sensors/thinlens.cpp, orthographic.cpp, telecentric.cpp: sampleRayDifferential; the
-// pinhole kernels keep their own prologue, which this change leaves alone), the single
-// source of the camera ray of every MTSG_FEAT_LENS kernel: PathShader::produce (the
-// megakernel and the wavefront engine), direct_kernel and field_kernel, and of the
-// differential directions the environment lookup of a missed camera ray takes.
+// dsensor.h -- the primary ray of the projective sensors (src/sensors/perspective.cpp,
+// thinlens.cpp, orthographic.cpp, telecentric.cpp: sampleRayDifferential), the single
+// source of the camera ray of every kernel: PathShader::produce (the megakernel and the
+// wavefront engine), direct_kernel and field_kernel, and of the differential directions
+// the environment lookup of a missed camera ray takes.  `perspective` has its own
+// functions (pinhole_*, camera_ray), which every kernel but the MTSG_FEAT_LENS ones runs;
+// those run sensor_ray / sensor_ray_diff.  (The pinhole's differentials stay written out in
+// PathShader::shade and path_kernel.hip's env_camera: through a shared function either
+// caller compiled to other code.)
 //
 // The sensor type is a run-time field (MtsgCameraLens, MtsgLaunch::cam_lens).  `thinlens` and `telecentric` set
 // ENeedsApertureSample: renderBlock (integrator.cpp:165-186) draws rRec.nextSample2D() for
@@ -11,8 +14,17 @@
 // (ax, ay) and every later sampler dimension of the sample moves by two.  There is no time
 // sample (shutterOpen == shutterClose).
 //
-// Included by dpath.h after xf_point; the disk warp is danalytic.h's, its sincosf glibc's.
+// Included by dpath.h; the disk warp is danalytic.h's, its sincosf glibc's.
 #pragma once
+
+__device__ __forceinline__ f3 xf_point(const float *m, f3 p) {         // transform.h:108-125
+    float x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
+    float y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
+    float z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
+    float w = m[12] * p.x + m[13] * p.y + m[14] * p.z + m[15];
+    if (w == 1.0f) return mk(x, y, z);
+    return divs(mk(x, y, z), w);
+}
 
 __device__ __forceinline__ bool sensor_needs_aperture(const MtsgCameraLens &ln) {
     return ln.type == MTSG_SENSOR_THINLENS || ln.type == MTSG_SENSOR_TELECENTRIC;
@@ -29,6 +41,34 @@ __device__ __forceinline__ f3 xf_vector(const float *m, f3 v) {
               m[8] * v.x + m[9] * v.y + m[10] * v.z);
 }
 
+// The pinhole: PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298).
+// nearP of film position (sx, sy), which thinlens shares
+__device__ __forceinline__ f3 sensor_near_point(const MtsgCamera &cam, float sx, float sy) {
+    return xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
+}
+// the ray's direction in camera space and invZ = 1 / its z: the world direction is
+// xf_vector(to_world, .), the interval [near_clip, far_clip] * invZ
+__device__ __forceinline__ f3 pinhole_dir(const MtsgCamera &cam, float sx, float sy, float &invZ) {
+    const f3 dl = normalize(sensor_near_point(cam, sx, sy));
+    invZ = 1.0f / dl.z;
+    return dl;
+}
+// every pinhole ray's origin, toWorld(0, 0, 0) (wave-uniform)
+__device__ __forceinline__ f3 pinhole_origin(const MtsgCamera &cam) {
+    const float *W = cam.to_world;
+    return mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
+              W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);
+}
+// origin, direction, [mint, maxt]
+__device__ __forceinline__ void camera_ray(const MtsgCamera &cam, float sx, float sy, f3 &ro, f3 &rd, float &mint,
+                                           float &maxt) {
+    float invZ;
+    const f3 dl = pinhole_dir(cam, sx, sy, invZ);
+    mint = cam.near_clip * invZ;
+    maxt = cam.far_clip * invZ;
+    ro = pinhole_origin(cam);
+    rd = xf_vector(cam.to_world, dl);
+}
 // the aperture point of (ax, ay): squareToUniformDiskConcentric(apertureSample) * radius
 __device__ __forceinline__ void sensor_aperture(const MtsgCameraLens &ln, float ax, float ay, float &tx, float &ty) {
     float dx, dy;
@@ -86,7 +126,7 @@ __device__ __forceinline__ void sensor_ray_diff(const MtsgCamera &cam, const Mts
         rxd = ryd = rd;
     } else {
         const float *W = cam.to_world;
-        const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
+        const f3 nearP = sensor_near_point(cam, sx, sy);
         f3 ap = mk(0.0f, 0.0f, 0.0f);   // thinlens: focusPx, focusPy seen from the aperture point
         sensor_aperture(ln, ax, ay, ap.x, ap.y);
         const float fDist = ln.focus_distance / nearP.z;

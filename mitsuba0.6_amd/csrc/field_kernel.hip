@@ -6,7 +6,7 @@
 // read off that one record.  The prologue is direct_kernel's (path_kernel.hip), so a field
 // sample sits at the position, and sees the hit, of the colour render's sample.
 //
-// Each field is recorded as {f.r, f.g, f.b, alpha, 1} through film_record (dpath.h) into its
+// Each field is recorded as {f.r, f.g, f.b, alpha, 1} through film_record (dfilm.h) into its
 // own record array and summed by film_reduce / film_gather into its own ordinary 5-float
 // film.  multichannel's blocks are built with warnInvalid off (multichannel.cpp:143-145):
 // negative values (normals, positions) are kept, film_record<false>.
@@ -14,21 +14,6 @@
 // Built with path_kernel.hip's flags (Makefile PK_FLAGS): it inlines the same traversal.
 #include "dpath.h"
 #include "launchers.h"
-
-// PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298), as path_kernel.hip's
-__device__ __forceinline__ void field_camera_ray(const MtsgCamera &cam, float sx, float sy, f3 &ro, f3 &rd,
-                                                 float &mint, float &maxt) {
-    const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
-    const f3 dl = normalize(nearP);
-    const float invZ = 1.0f / dl.z;
-    mint = cam.near_clip * invZ;
-    maxt = cam.far_clip * invZ;
-    const float *W = cam.to_world;
-    ro = mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
-            W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);
-    rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
-            W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
-}
 
 // BSDF::getDiffuseReflectance(its) of the hit shape's BSDF
 __device__ __forceinline__ f3 field_albedo(const MtsgDeviceScene &S, GBsdf &top, const Hit &h) {
@@ -59,7 +44,7 @@ __device__ __forceinline__ f3 field_albedo(const MtsgDeviceScene &S, GBsdf &top,
 template <bool SCENE_LDS, int FEAT>
 __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLaunch L, MtsgFieldArgs FA) {
     constexpr bool ANA = (FEAT & MTSG_FEAT_ANA) != 0;
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     const LdsView<SCENE_LDS> V = stage_lds<SCENE_LDS>(L, lds);   // ends with a barrier
     lds_u32 *ycolTab = V.ycolTab;
@@ -73,21 +58,13 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
 
     const uint64_t lanes = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t it = (uint64_t)xcd_block(L.xcds) * BLOCK + threadIdx.x; it < L.num_items; it += lanes) {
-        const uint32_t jj = (uint32_t)(it / L.num_pixels);
-        const uint32_t pix = (uint32_t)(it - (uint64_t)jj * L.num_pixels);
+        uint32_t jj, pix;
         int px, py;
-        if (!pixel_of(L, pix, px, py)) continue;
+        if (!item_pixel(L, it, jj, pix, px, py)) continue;
         const uint32_t j = L.j0 + jj;
         SamplerState smp;
-        smp.dim = 0;
-        smp.sampleIndex = j;
-        smp.err = false;
-        smp.sobolIndex = SC.indep ? indep_key((uint32_t)px, (uint32_t)py, j)
-                       : (L.lut.m > 1) ? sobol_lookup_lds(L.lut, ycolTab, L.nibbles, j, (uint32_t)px, (uint32_t)py,
-                                                          L.scramble64)
-                                       : (uint64_t)j;
         float u, v;
-        next2d(SC, L.resolution, smp, px, py, u, v);
+        sample_start(SC, L, ycolTab, L.nibbles, px, py, j, smp, u, v);
         const float sx = (float)px + u, sy = (float)py + v;
         f3 ro, rd;
         float rmint, rmaxt;
@@ -97,28 +74,18 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
             if (sensor_needs_aperture(L.cam_lens)) next2d(SC, L.resolution, smp, px, py, ax, ay);
             sensor_ray(S.cam, L.cam_lens, sx, sy, ax, ay, ro, rd, rmint, rmaxt);
         } else {
-            field_camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
+            camera_ray(S.cam, sx, sy, ro, rd, rmint, rmaxt);
         }
 
         // rRec.rayIntersect(sensorRay): the one closest-hit query of the sample
-        float mint, maxt;
         uint32_t slot = 0, prim = 0;
         float hu = 0, hv = 0, ht = 0;
-        bool hit = false;
-        if (ray_interval(S, ro, rd, rmint, rmaxt, false, mint, maxt)) {
-            if (SCENE_LDS && L.scan)
-                hit = scan_tris<false, false>(L, ro, rd, mint, maxt, slot, hu, hv, ht, cT);
-            else if (SCENE_LDS)
-                hit = traverse<false, false, ANA>(ldsNodes, ldsTris, ro, rd, mint, maxt, stkN, stkD, slot, hu, hv, ht,
-                                                  cN, cT, S.analytic);
-            else
-                hit = traverse<false, false, ANA>((glb_node *)S.nodes, (glb_tri *)S.tris, ro, rd, mint, maxt, stkN,
-                                                  stkD, slot, hu, hv, ht, cN, cT, S.analytic);
-        }
+        const bool hit = closest_hit<SCENE_LDS, ANA>(L, ldsNodes, ldsTris, stkN, stkD, ro, rd, rmint, rmaxt, slot, hu, hv,
+                                                     ht, cN, cT);
         Hit its = Hit{};
         bool analytic = false;
         if (hit) {
-            prim = (SCENE_LDS && L.scan) ? slot : SCENE_LDS ? ldsTris[slot].prim : S.tris[slot].prim;
+            prim = hit_prim<SCENE_LDS>(L, ldsTris, slot);
             fill_hit<true, ANA>(S, hs, slot, prim, hu, hv, ht, ro, rd, its);
             if constexpr (ANA) analytic = hs.shapes[its.shape].analytic >= 0;
         }

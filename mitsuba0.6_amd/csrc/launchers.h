@@ -20,10 +20,7 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L);   // dynamic LDS of the megaker
 bool mtsg_path_start_queue(const MtsgLaunch &L);   // the launch starts its paths from the LDS queue (dpath.h mtsg_start_queue)
 // one object per scene feature set: the megakernel instantiation for L, BSDF-set bits `bits`
 #define MTSG_PATH_F_DECL(N) PathKernelFn mtsg_path_pick_f##N(const MtsgLaunch &L, int bits, bool instr);
-MTSG_PATH_F_DECL(0) MTSG_PATH_F_DECL(1) MTSG_PATH_F_DECL(2) MTSG_PATH_F_DECL(3) MTSG_PATH_F_DECL(6) MTSG_PATH_F_DECL(7)
-MTSG_PATH_F_DECL(1031)   // MTSG_FEAT_SET_DELTA: scenes with delta emitters
-MTSG_PATH_F_DECL(3079)   // MTSG_FEAT_SET_LENS: scenes whose sensor is not `perspective`
-MTSG_PATH_F_DECL(7175)   // MTSG_FEAT_SET_COMBO: scenes with a mixturebsdf, blendbsdf or mask
+MTSG_FEAT_SETS(MTSG_PATH_F_DECL)   // (layout.h)
 #undef MTSG_PATH_F_DECL
 hipError_t mtsg_launch_gather(const MtsgLaunch &L, hipStream_t stream);
 hipError_t mtsg_launch_reduce(const MtsgLaunch &L, hipStream_t stream);
@@ -72,7 +69,6 @@ uint32_t mtsg_launch_bytes_path_kernel();
 uint32_t mtsg_launch_bytes_wf_kernel();
 uint32_t mtsg_launch_bytes_field_kernel();
 #define MTSG_BYTES_DECL(N) uint32_t mtsg_launch_bytes_path_f##N(); uint32_t mtsg_launch_bytes_wf_shade_f##N();
-MTSG_BYTES_DECL(0) MTSG_BYTES_DECL(1) MTSG_BYTES_DECL(2) MTSG_BYTES_DECL(3) MTSG_BYTES_DECL(6) MTSG_BYTES_DECL(7)
-MTSG_BYTES_DECL(1031) MTSG_BYTES_DECL(3079) MTSG_BYTES_DECL(7175)
+MTSG_FEAT_SETS(MTSG_BYTES_DECL)
 #undef MTSG_BYTES_DECL
 }

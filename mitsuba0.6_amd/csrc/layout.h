@@ -151,6 +151,23 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
 #define MTSG_FEAT_SET_DELTA (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA | MTSG_FEAT_DELTA)   // = 1031
 #define MTSG_FEAT_SET_LENS (MTSG_FEAT_SET_DELTA | MTSG_FEAT_LENS)                               // = 3079
 #define MTSG_FEAT_SET_COMBO (MTSG_FEAT_SET_LENS | MTSG_FEAT_COMBO)                              // = 7175
+// The scene feature sets the megakernel (path_f<N>.o), direct_kernel and the wavefront shade
+// kernels (wf_shade_f<N>.o) are compiled for, as the numbers the object and function names
+// carry: the one list the declarations, the launch-record check and the picks come from.
+// A pick takes a set by its exact value; any other combination of ENV | EXT | ANA runs set 7,
+// which holds them all, as its `default:` (MTSG_FEAT_SETS_BUT_7 generates the cases).
+// The Makefile's WF_FEATS names the same sets for the build.
+#define MTSG_FEAT_SETS_BUT_7(X) X(0) X(1) X(2) X(3) X(6) X(1031) X(3079) X(7175)
+#define MTSG_FEAT_SETS(X) X(0) X(1) X(2) X(3) X(6) X(7) X(1031) X(3079) X(7175)
+static_assert(7 == (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA), "set 7 holds ENV, EXT and ANA");
+static_assert(1031 == MTSG_FEAT_SET_DELTA && 3079 == MTSG_FEAT_SET_LENS && 7175 == MTSG_FEAT_SET_COMBO,
+              "MTSG_FEAT_SETS names the delta, lens and combo sets by value");
+// whether n is one of MTSG_FEAT_SETS (path_f.hip, wf_shade_f.hip: their -D value)
+constexpr bool mtsg_is_feat_set(int n) {
+#define MTSG_FEAT_IS(N) n == N ||
+    return MTSG_FEAT_SETS(MTSG_FEAT_IS) false;
+#undef MTSG_FEAT_IS
+}
 enum { MTSG_INTEGRATOR_PATH = 0, MTSG_INTEGRATOR_DIRECT = 1, MTSG_INTEGRATOR_VOLPATH = 2 };   // = MTSGPU_INTEGRATOR_*
 enum { MTSG_SAMPLER_SOBOL = 0, MTSG_SAMPLER_INDEPENDENT = 1, MTSG_SAMPLER_SFMT_REPLAY = 2,
        MTSG_SAMPLER_SFMT_BLOCKS = 3 };    // = MTSGPU_SAMPLER_*
@@ -302,7 +319,7 @@ struct MtsgLookup {
 // capacity `cap` = slots, so one wave's append is one atomic on one of 8
 // counters and a region can never overflow; consumers walk the concatenation.
 #define MTSG_WF_STATE_VECS 8          // float4 state vectors per slot (AoS: one slot = 128 B)
-#define MTSG_WF_HIT_VECS 6            // float4 per precomputed hit record (dpath.h hit_store)
+#define MTSG_WF_HIT_VECS 6            // float4 per precomputed hit record (dhit.h hit_store)
 #define MTSG_WF_NONE 0xffffffffu      // hit record prim: no hit
 #define MTSG_WF_REGIONS 8
 #ifndef MTSG_WF_LDS_STACK
@@ -401,7 +418,7 @@ struct MtsgLaunch {
     float *film_own;                  // fw*fh*5: own-pixel sums (ordered reduction), or the gathered film
     double *film_spill;               // fw*fh*5: splats into other pixels (every filter outside gather mode), double
                                       // atomics: a pixel's neighbour splats sum exactly, in any order, while
-                                      // sum|c| < 2^(q + 53) (dpath.h film_splat); wide gaussians leave that regime
+                                      // sum|c| < 2^(q + 53) (dfilm.h film_splat); wide gaussians leave that regime
     // gather mode (filters whose footprint covers neighbours, e.g. gaussian): the kernels store
     // each sample's value and position; film_gather<H> forms every pixel's sum in a fixed order
     uint32_t gather;                  // 1: gather mode

@@ -15,6 +15,7 @@
 // orthographic or telecentric (dsensor.h): the generic kernel alone as well.
 #include "dmega.h"
 
+static_assert(mtsg_is_feat_set(PATH_FEAT), "-DPATH_FEAT names a set of layout.h's MTSG_FEAT_SETS");
 #define PF_NAME2(a, N) a##N
 #define PF_NAME(a, N) PF_NAME2(a, N)
 

@@ -37,21 +37,6 @@ __device__ __forceinline__ void sobol_array2d(const SobolCtx &C, const MtsgLooku
     v = sobol_sample(C, idx, dim + 1);
 }
 
-// PerspectiveCameraImpl::sampleRayDifferential (perspective.cpp:271-298): origin, direction, [mint, maxt]
-__device__ __forceinline__ void camera_ray(const MtsgCamera &cam, float sx, float sy, f3 &ro, f3 &rd, float &mint,
-                                           float &maxt) {
-    const f3 nearP = xf_point(cam.sample_to_camera, mk(sx * cam.inv_res_x, sy * cam.inv_res_y, 0.0f));
-    const f3 dl = normalize(nearP);
-    const float invZ = 1.0f / dl.z;
-    mint = cam.near_clip * invZ;
-    maxt = cam.far_clip * invZ;
-    const float *W = cam.to_world;
-    ro = mk(W[0] * 0.0f + W[1] * 0.0f + W[2] * 0.0f + W[3], W[4] * 0.0f + W[5] * 0.0f + W[6] * 0.0f + W[7],
-            W[8] * 0.0f + W[9] * 0.0f + W[10] * 0.0f + W[11]);
-    rd = mk(W[0] * dl.x + W[1] * dl.y + W[2] * dl.z, W[4] * dl.x + W[5] * dl.y + W[6] * dl.z,
-            W[8] * dl.x + W[9] * dl.y + W[10] * dl.z);
-}
-
 // Scene::evalEnvironment of a camera ray with its (scaled) differentials
 __device__ __forceinline__ f3 env_camera(const MtsgLaunch &L, float sx, float sy, f3 rd) {
     glb_env *E = (glb_env *)L.scene.env;
@@ -179,22 +164,6 @@ __device__ __forceinline__ NeeSample emitter_sample(const MtsgDeviceScene &S, co
     return r;
 }
 
-// Scene::pdfEmitterDirect for an area-light hit h reached along d from `ref`
-// (area.cpp:175-181, shape.cpp:117-126 / sphere.cpp:357-387, scene.h:848-850)
-template <bool ANA>
-__device__ __forceinline__ float area_hit_pdf(const MtsgDeviceScene &S, const Hit &h, f3 ref, f3 d, f3 refN) {
-    const MtsgEmitter &e = S.emitters[S.shapes[h.shape].emitter];
-    const f3 dn = h.sh.n;
-    float pdf = 0.0f;
-    if (dot(d, refN) >= 0 && dot(d, dn) < 0) {
-        if (ANA && S.shapes[h.shape].analytic >= 0)
-            pdf = ana_pdf_direct(((GAna *)S.analytic)[S.shapes[h.shape].analytic], ref, d, dn, h.t);
-        else
-            pdf = e.inv_area * (h.t * h.t) / absdot(d, dn);
-    }
-    return pdf * (e.weight * S.em_norm);
-}
-
 // BSDF eval/pdf/sample through a twosided wrapper (twosided.cpp:105-172)
 template <bool EXT>
 __device__ __forceinline__ void bsdf_eval_pdf_2s(const MtsgDeviceScene &S, GBsdf &bsdf, const Hit &h, f3 wo, f3 &val,
@@ -259,7 +228,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                    ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0,
                    LENS = (FEAT & MTSG_FEAT_LENS) != 0,   // the sensor's own ray (dsensor.h)
                    COMBO = (FEAT & MTSG_FEAT_COMBO) != 0; // mixturebsdf / blendbsdf / mask (dcombo.h)
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     // the delta-emitter feature set is compiled with ENV; its scenes need not have an environment
     const bool haveEnv = !DELTA || S.env_emitter >= 0;
@@ -278,26 +247,12 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
     // closest hit / occlusion through the scene's structure (scan, LDS BVH or HBM BVH)
     auto closest = [&](f3 o, f3 d, float rmint, float rmaxt, Hit &h) -> bool {
         cRays++;
-        float mint, maxt;
         uint32_t slot = 0;
         float hu = 0, hv = 0, ht = 0;
-        bool hit = false;
-        if (ray_interval(S, o, d, rmint, rmaxt, false, mint, maxt)) {
-            if (SCENE_LDS && L.scan)
-                hit = scan_tris<false, false>(L, o, d, mint, maxt, slot, hu, hv, ht, cT);
-            else if (SCENE_LDS)
-                hit = traverse<false, false, ANA>(ldsNodes, ldsTris, o, d, mint, maxt, stkN, stkD, slot, hu, hv, ht, cN,
-                                                  cT, S.analytic);
-            else
-                hit = traverse<false, false, ANA>((glb_node *)S.nodes, (glb_tri *)S.tris, o, d, mint, maxt, stkN, stkD,
-                                                  slot, hu, hv, ht, cN, cT, S.analytic);
-        }
-        if (hit) {
-            const uint32_t prim = (SCENE_LDS && L.scan) ? slot : SCENE_LDS ? ldsTris[slot].prim : S.tris[slot].prim;
-            fill_hit<EXT, ANA>(S, hs, slot, prim, hu, hv, ht, o, d, h);
-        } else {
-            h = Hit{};
-        }
+        const bool hit = closest_hit<SCENE_LDS, ANA>(L, ldsNodes, ldsTris, stkN, stkD, o, d, rmint, rmaxt, slot, hu, hv, ht,
+                                                     cN, cT);
+        if (hit) fill_hit<EXT, ANA>(S, hs, slot, hit_prim<SCENE_LDS>(L, ldsTris, slot), hu, hv, ht, o, d, h);
+        else h = Hit{};
         return hit;
     };
     auto occluded = [&](f3 o, f3 d, float dist) -> bool {   // Ray(ref, d, Epsilon, dist*(1-ShadowEpsilon))
@@ -315,11 +270,12 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
 
     const uint64_t lanes = (uint64_t)gridDim.x * BLOCK;
     for (uint64_t it = (uint64_t)xcd_block(L.xcds) * BLOCK + threadIdx.x; it < L.num_items; it += lanes) {
-        const uint32_t jj = (uint32_t)(it / L.num_pixels);
-        const uint32_t pix = (uint32_t)(it - (uint64_t)jj * L.num_pixels);
+        uint32_t jj, pix;
         int px, py;
-        if (!pixel_of(L, pix, px, py)) continue;
+        if (!item_pixel(L, it, jj, pix, px, py)) continue;
         const uint32_t j = L.j0 + jj;
+        // dsampler.h sample_start, spelled out: through that function the MTSG_FEAT_SET_COMBO
+        // instantiation of this kernel compiles to other code
         SamplerState smp;
         smp.dim = 0;
         smp.sampleIndex = j;
@@ -410,7 +366,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                     if (closest(its.p, wo, D_EPSILON, INFINITY, h2)) {
                         if (hs.shapes[h2.shape].emitter < 0) continue;
                         value = area_Le(S, h2, neg(wo));
-                        if (!(bs.sampledType & MTSG_F_DELTA)) lumPdf = area_hit_pdf<ANA>(S, h2, its.p, wo, refN);
+                        if (!(bs.sampledType & MTSG_F_DELTA)) lumPdf = area_hit_pdf<ANA>(&S, S.shapes[h2.shape].emitter, h2, its.p, wo, refN);
                     } else {
                         if (!ENV || !haveEnv || (L.hide_emitters && bs.sampledType == MTSG_F_NULL)) continue;
                         glb_env *E = (glb_env *)S.env;
@@ -453,7 +409,7 @@ template <bool ANY, int WAVES, bool ANA>
 __global__ __launch_bounds__(BLOCK, WAVES) void trace_kernel(MtsgDeviceScene S, const float4 *__restrict__ rays,
                                                               uint32_t n, float4 *__restrict__ out,
                                                               uint32_t stackDepth) {
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     lds_stk_n *stkN = (lds_stk_n *)lds + threadIdx.x;
     lds_stk_d *stkD = (lds_stk_d *)(lds + stackDepth * BLOCK) + threadIdx.x;
     unsigned long long cn = 0, ct = 0;
@@ -795,15 +751,10 @@ static int spec_bits(const MtsgLaunch &L) {
 // mtsg_launch_path launches it, mtsg_path_kernel_occupancy sizes the grid by it
 static PathKernelFn path_pick(const MtsgLaunch &L, bool instr) {
     const int bits = spec_bits(L);
-    switch (mtsg_path_features(L)) {
-        case 0: return mtsg_path_pick_f0(L, bits, instr);
-        case MTSG_FEAT_ENV: return mtsg_path_pick_f1(L, bits, instr);
-        case MTSG_FEAT_EXT: return mtsg_path_pick_f2(L, bits, instr);
-        case MTSG_FEAT_ENV | MTSG_FEAT_EXT: return mtsg_path_pick_f3(L, bits, instr);
-        case MTSG_FEAT_EXT | MTSG_FEAT_ANA: return mtsg_path_pick_f6(L, bits, instr);
-        case MTSG_FEAT_SET_DELTA: return mtsg_path_pick_f1031(L, bits, instr);
-        case MTSG_FEAT_SET_LENS: return mtsg_path_pick_f3079(L, bits, instr);
-        case MTSG_FEAT_SET_COMBO: return mtsg_path_pick_f7175(L, bits, instr);
+    switch (mtsg_path_features(L)) {   // (layout.h MTSG_FEAT_SETS)
+#define MTSG_PATH_CASE(N) case N: return mtsg_path_pick_f##N(L, bits, instr);
+        MTSG_FEAT_SETS_BUT_7(MTSG_PATH_CASE)
+#undef MTSG_PATH_CASE
         default: return mtsg_path_pick_f7(L, bits, instr);
     }
 }
@@ -819,15 +770,10 @@ hipError_t mtsg_launch_path(const MtsgLaunch &L, int grid, bool samples, bool st
     const bool instr = samples || stats;
     if (L.integrator == MTSG_INTEGRATOR_DIRECT) {
         switch (mtsg_path_features(L)) {
-            case 0: launch_direct<0>(L, grid, stream); break;
-            case MTSG_FEAT_ENV: launch_direct<MTSG_FEAT_ENV>(L, grid, stream); break;
-            case MTSG_FEAT_EXT: launch_direct<MTSG_FEAT_EXT>(L, grid, stream); break;
-            case MTSG_FEAT_ENV | MTSG_FEAT_EXT: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT>(L, grid, stream); break;
-            case MTSG_FEAT_EXT | MTSG_FEAT_ANA: launch_direct<MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
-            case MTSG_FEAT_SET_DELTA: launch_direct<MTSG_FEAT_SET_DELTA>(L, grid, stream); break;
-            case MTSG_FEAT_SET_LENS: launch_direct<MTSG_FEAT_SET_LENS>(L, grid, stream); break;
-            case MTSG_FEAT_SET_COMBO: launch_direct<MTSG_FEAT_SET_COMBO>(L, grid, stream); break;
-            default: launch_direct<MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA>(L, grid, stream); break;
+#define MTSG_DIRECT_CASE(N) case N: launch_direct<N>(L, grid, stream); break;
+            MTSG_FEAT_SETS_BUT_7(MTSG_DIRECT_CASE)
+#undef MTSG_DIRECT_CASE
+            default: launch_direct<7>(L, grid, stream); break;
         }
         return hipGetLastError();
     }

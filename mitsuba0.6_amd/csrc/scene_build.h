@@ -68,7 +68,7 @@ struct HostScene {
 
 // Returns MTSGPU_OK or an error code; `err` receives the message.
 int mtsg_configure_scene(const mtsgpu_scene_desc *desc, HostScene &out, std::string &err);
-// the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dpath.h); configure_shape.cpp
+// the unit face normal of triangle (p0, p1, p2), by fill_hit's float operations (dhit.h); configure_shape.cpp
 void mtsg_face_normal(const float *p0, const float *p1, const float *p2, float *n);
 bool mtsg_invert4(const float *m16, float *inv16);   // Matrix4x4::invert, row-major; configure_shape.cpp
 void mtsg_build_qnodes(HostScene &S);   // host export only (mtsgpu_bvh_host); bvh_build.cpp

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void wf_shade(MtsgLaunch L, MtsgWave 
     Q.load(wf_cnt(W, W.parity, 2 + queue));
     const uint32_t n = W.seed ? W.slots : Q.total();
     if (blockIdx.x * BLOCK >= n) return;   // block-uniform
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     __shared__ uint32_t red[BLOCK / 64 * 16];
     wf_shade_block<INSTR, FEAT, KIND, HITK>(L, W, part, queue, Q, n, blockIdx.x, lds, red);
 }
@@ -313,7 +313,7 @@ constexpr uint32_t wf_kd_lds_lane_bytes(int kdk, bool kdmb) { return (uint32_t)k
 template <bool STATS, bool SCENE_LDS, bool ANA, bool KD, int KDK = 0, bool KDMB = false>
 __global__ __launch_bounds__(BLOCK, KD ? (wf_kd_lds_lane_bytes(KDK, KDMB) > 80 ? 4 : MTSG_WF_KD_TRACE_WAVES) : MTSG_WF_TRACE_WAVES) void wf_trace(
     MtsgLaunch L, MtsgWave W, unsigned long long *part) {
-    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dpath.h sobol_row)
+    extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     __shared__ uint32_t red[BLOCK / 64 * 16];
     const MtsgDeviceScene &S = L.scene;
     const uint32_t p = W.parity, region = blockIdx.x % WF_R;

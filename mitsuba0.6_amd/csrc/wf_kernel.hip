@@ -7,8 +7,7 @@
 #include <cstdlib>
 
 #define MTSG_WF_PICK_DECL(N) WfShadeFn mtsg_wf_pick_##N(int wk, bool instr, bool ggx);
-MTSG_WF_PICK_DECL(0) MTSG_WF_PICK_DECL(1) MTSG_WF_PICK_DECL(2) MTSG_WF_PICK_DECL(3) MTSG_WF_PICK_DECL(6)
-MTSG_WF_PICK_DECL(7) MTSG_WF_PICK_DECL(1031) MTSG_WF_PICK_DECL(3079) MTSG_WF_PICK_DECL(7175)
+MTSG_FEAT_SETS(MTSG_WF_PICK_DECL)   // (layout.h)
 #undef MTSG_WF_PICK_DECL
 
 // the per-block partial counters of a chunk -> MtsgLaunch::counters
@@ -42,15 +41,10 @@ size_t mtsg_wf_trace_lds_bytes(const MtsgLaunch &L) {
 }
 
 static WfShadeFn wf_shade_pick(const MtsgLaunch &L, int wk, bool instr, bool ggx) {
-    switch (mtsg_path_features(L)) {   // = MTSG_FEAT_ENV | EXT | ANA bits
-        case 0: return mtsg_wf_pick_0(wk, instr, ggx);
-        case 1: return mtsg_wf_pick_1(wk, instr, ggx);
-        case 2: return mtsg_wf_pick_2(wk, instr, ggx);
-        case 3: return mtsg_wf_pick_3(wk, instr, ggx);
-        case 6: return mtsg_wf_pick_6(wk, instr, ggx);
-        case MTSG_FEAT_SET_DELTA: return mtsg_wf_pick_1031(wk, instr, ggx);
-        case MTSG_FEAT_SET_LENS: return mtsg_wf_pick_3079(wk, instr, ggx);
-        case MTSG_FEAT_SET_COMBO: return mtsg_wf_pick_7175(wk, instr, ggx);
+    switch (mtsg_path_features(L)) {   // (layout.h MTSG_FEAT_SETS)
+#define MTSG_WF_CASE(N) case N: return mtsg_wf_pick_##N(wk, instr, ggx);
+        MTSG_FEAT_SETS_BUT_7(MTSG_WF_CASE)
+#undef MTSG_WF_CASE
         default: return mtsg_wf_pick_7(wk, instr, ggx);
     }
 }

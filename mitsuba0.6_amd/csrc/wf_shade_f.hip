@@ -4,6 +4,7 @@
 #include "wf_impl.h"
 #include "launchers.h"
 
+static_assert(mtsg_is_feat_set(WF_FEAT), "-DWF_FEAT names a set of layout.h's MTSG_FEAT_SETS");
 #define MTSG_WF_PICK_NAME2(N) mtsg_wf_pick_##N
 #define MTSG_WF_PICK_NAME(N) MTSG_WF_PICK_NAME2(N)
 #define MTSG_WF_BYTES_NAME2(N) mtsg_launch_bytes_wf_shade_f##N

@@ -1,5 +1,5 @@
 """numpy restatement of the film order taken when gather mode is off (box filters, gaussians
-with H = 0 or H > MTSG_GATHER_HMAX, MTSGPU_NO_GATHER): dpath.h film_splat + film_reduce +
+with H = 0 or H > MTSG_GATHER_HMAX, MTSGPU_NO_GATHER): dfilm.h film_splat + film_reduce +
 film_finalize on the GPU, film_put in the oracle.
 
 Per film value the sum has two parts:

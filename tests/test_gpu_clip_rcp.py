@@ -1,4 +1,4 @@
-"""One reciprocal per ray and axis (dpath.h aabb_clip -> scan_pair): the scene-bounds clip
+"""One reciprocal per ray and axis (dtraverse.h aabb_clip -> dscan.h scan_pair): the scene-bounds clip
 hands its three 1 / d to the tiny-scene scan, which divides by them in its axis-aligned
 groups instead of forming them again.  Scan scenes (<= 64 triangles) in which the clip's
 paths differ between the lanes of one wave:

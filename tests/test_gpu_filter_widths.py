@@ -8,7 +8,7 @@ a. film_gather<1>, <3> and <4> (stddev 0.2, 0.8, 1.0): two rows per thread with 
    order (tests/test_film_gather.py gather_ref) -- which differs from the other order in most
    pixels (tests/test_film_spill.py), so equality shows which kernel ran.
 b. MTSGPU_NO_GATHER takes the same filter through the fallback.
-c. The fallback (dpath.h film_splat's double atomics + film_finalize): gaussians with H = 0,
+c. The fallback (dfilm.h film_splat's double atomics + film_finalize): gaussians with H = 0,
    5, 6 and boxes of radius 0.3 and 1.5, against tests/film_ref.py spill_film_ref of the
    oracle's records.  Film values whose spill sum is certified exact are compared bit for
    bit; the others within 3 * 2^-23 of the larger value: the two double totals round to

@@ -1,5 +1,5 @@
 """The tiny-scene scan over the canonical-zero copy of the records (render_plan.cpp
-mtsg_scan_layout, dpath.h scan_pair_k / scan_k): the scan's copy of a general record has
+mtsg_scan_layout, dscan.h scan_pair_k / scan_k): the scan's copy of a general record has
 +0 for a -0 n_u / n_v (n_d != 0), which pairs two more of the Cornell box's faces.  No
 scan can tell the copy from the source, so every render must still equal the oracle's
 (which keeps the source records) bit for bit: per-sample records, film and counters,

@@ -1,4 +1,4 @@
-"""scan_pair's plane pairs (dpath.h scan_pair_k, render_plan.cpp mtsg_scan_layout): the
+"""scan_pair's plane pairs (dscan.h scan_pair_k, render_plan.cpp mtsg_scan_layout): the
 two records of a fan-triangulated quad share plane and vertex A, so a bounce's
 pass forms their t, hu and hv once.  Every lane must end with what the
 record-by-record scan gives it: per-sample records and films bit-identical to

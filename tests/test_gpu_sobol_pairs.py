@@ -1,4 +1,4 @@
-"""next2d's paired Sobol draws (dpath.h sobol_sample2): two successive dimensions of one
+"""next2d's paired Sobol draws (dsampler.h sobol_sample2): two successive dimensions of one
 index share their row addresses when both tables are staged in LDS; a pair that straddles
 the staged dimensions, tables in global memory, the independent sampler and the SFMT
 replay draw as before.  The pairs of a path are (0,1), (2,3), (5,6), ... (dimension 4 is

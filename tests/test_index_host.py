@@ -154,7 +154,7 @@ def test_folded_lookup_matches_recorded_indices():
 
 # ---- the unit face normals staged with an LDS scene -------------------------------------
 def _face_normal_f32(c):
-    """fill_hit's operation sequence (dpath.h) in numpy float32: cross as dmath.h forms it,
+    """fill_hit's operation sequence (dhit.h) in numpy float32: cross as dmath.h forms it,
     the length by a correctly rounded sqrt, its reciprocal, three products; zero stays zero."""
     f = np.float32
     a, b = c[1] - c[0], c[2] - c[0]

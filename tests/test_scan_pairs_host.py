@@ -2,7 +2,7 @@
 mtsgpu_scan_host (no device): records grouped by projection axis and aligned
 flag, each group led by its plane pairs -- records that share plane and vertex
 A bit for bit, partners adjacent -- with the singles after them
-(render_plan.cpp mtsg_scan_layout, dpath.h scan_pair_k)."""
+(render_plan.cpp mtsg_scan_layout, dscan.h scan_pair_k)."""
 import numpy as np
 import pytest
 

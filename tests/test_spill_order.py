@@ -1,5 +1,5 @@
 """Box-filter neighbour splats (the spill film) sum in double on both sides
-(dpath.h film_splat, oracle film_put), so a pixel's spill total does not depend
+(dfilm.h film_splat, oracle film_put), so a pixel's spill total does not depend
 on the order its contributions land -- as long as every partial sum is exact,
 which holds when sum|c| < 2^(q + 53) for q the smallest exponent of a lowest
 set mantissa bit among the contributions (tests/film_ref.py certifies it per

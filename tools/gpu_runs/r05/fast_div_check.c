@@ -1,4 +1,4 @@
-/* Host check of div_by_rcp (csrc/dpath.h): a / b as a * RN(1/b) with two
+/* Host check of div_by_rcp (csrc/dscan.h): a / b as a * RN(1/b) with two
  * FMA residual corrections, against IEEE division, bit for bit, over the range
  * the scan's fast path admits (|b| in [2^-60, 2), quotients >= 2^-31 in
  * magnitude; smaller ones fall below every admitted mint).  Random signs,
