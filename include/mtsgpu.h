@@ -63,7 +63,13 @@ enum { /* BSDF plugins on the path (src/bsdfs) */
        -> leaf, every level optional; mtsgpu_check_scene / mtsgpu_upload_scene refuse the rest */
     MTSGPU_BSDF_MIXTURE = 8,         /* mixturebsdf.cpp (weighted sum of children[])      */
     MTSGPU_BSDF_BLEND = 9,           /* blendbsdf.cpp   (nested[0], nested[1] by 'weight') */
-    MTSGPU_BSDF_MASK = 10            /* mask.cpp        ('opacity' in front of nested[0])  */
+    MTSGPU_BSDF_MASK = 10,           /* mask.cpp        ('opacity' in front of nested[0])  */
+    /* further leaves (the MTSG_FEAT_LEAF2 kernels).  phong and roughdiffuse are one-sided
+       reflectors: they may be nested in twosided and below the combinators; difftrans may not
+       (refused at upload).  (11 is kept free for thindielectric, which is not implemented.) */
+    MTSGPU_BSDF_DIFFTRANS = 12,      /* difftrans.cpp      (diffuse transmission)          */
+    MTSGPU_BSDF_ROUGHDIFFUSE = 13,   /* roughdiffuse.cpp   (Oren-Nayar, both branches)     */
+    MTSGPU_BSDF_PHONG = 14           /* phong.cpp          (modified Phong + diffuse)      */
 };
 #define MTSGPU_MIXTURE_MAX 8         /* children of one mixturebsdf */
 
@@ -130,6 +136,16 @@ typedef struct {
        of nested[0]; ensure_energy_conservation scales an opacity above 1 */
     float opacity[3];
     mtsgpu_texture_desc opacity_tex;
+    /* ---- appended for types 12-14, as above: no earlier offset moved, the version stays 8.
+       Those types reuse the earlier fields: roughdiffuse reflectance / reflectance_tex and
+       alpha_u / alpha_tex (plugin default 0.2); phong diffuse_reflectance / reflectance_tex
+       (0.5) and specular_reflectance (0.2).  Textured parameters are checkerboards; a texture
+       on any other parameter of these three cannot be described and is refused where the
+       scene is read ---- */
+    float exponent;                 /* phong 'exponent' (default 30)               */
+    float transmittance[3];         /* difftrans 'transmittance' (default 0.5)     */
+    mtsgpu_texture_desc transmittance_tex;
+    int32_t use_fast_approx;        /* roughdiffuse 'useFastApprox' (default 0)    */
 } mtsgpu_bsdf_desc;
 
 enum { MTSGPU_EMITTER_AREA = 0,      /* area.cpp: on a shape (mesh_desc.emitter)          */
@@ -530,7 +546,8 @@ int mtsgpu_develop_ldr_device(mtsgpu_ctx *ctx, const mtsgpu_develop_ldr_params *
  * factor of its getDiffuseReflectance: plastic 1 - m_fdrExt (plastic.cpp:219-221),
  * roughplastic with a constant alpha m_externalRoughTransmittance->evalDiffuse(alpha)
  * (roughplastic.cpp:309-315), -1 for a textured alpha (evaluated per hit), 1 for
- * diffuse, 0 for every other BSDF.  factors: num_bsdfs floats. */
+ * diffuse, phong (its diffuseReflectance) and roughdiffuse (its reflectance), 0 for every other
+ * BSDF (difftrans: BSDF::getDiffuseReflectance's default).  factors: num_bsdfs floats. */
 int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, char *msg, size_t cap);
 /* (a scene with a mixturebsdf, blendbsdf or mask: MTSGPU_EINVAL, like the `albedo` field) */
 /* Host-only (no device needed): configure `scene` and copy what configure() derived for the
@@ -540,6 +557,18 @@ int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, c
  * NULL) its type flags, BSDF::EBSDFType bits.  Another BSDF type: MTSGPU_EINVAL. */
 int mtsgpu_combo_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out21, int32_t *flags, char *msg,
                       size_t cap);
+/* Host-only (no device needed): configure `scene` and copy what configure() derived for the
+ * leaf BSDF `bsdf` of type 12-14, the values the device will use.  out16: [0..2] the
+ * reflectance after ensureEnergyConservation (roughdiffuse 'reflectance', phong
+ * 'diffuseReflectance' in the pair form of phong.cpp:89-93, difftrans 'transmittance'; a
+ * textured one: color0 scaled), [3..5] the same texture's scaled color1 (= [0..2] for a
+ * constant), [6..8] phong's specularReflectance, [9..11] unused (0), [12] phong's
+ * m_specularSamplingWeight, [13] unused (0), [14] roughdiffuse's alpha (the constant; sigma =
+ * alpha.average() / sqrt(2) is formed per query) or phong's exponent, [15] roughdiffuse's
+ * useFastApprox, and the record's type flags (BSDF::EBSDFType bits) in *flags (may be NULL).
+ * Another BSDF type: MTSGPU_EINVAL. */
+int mtsgpu_leaf_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out16, int32_t *flags, char *msg,
+                     size_t cap);
 /* Batch ray queries on the uploaded scene, one GPU lane per ray:
  * Scene::rayIntersect (closest hit, shadow = 0) or the occlusion test
  * (shadow = 1) of ShapeKDTree::rayIntersect (src/librender/skdtree.cpp:

@@ -701,19 +701,28 @@ private:
         d.type = name == "diffuse" ? MTSGPU_BSDF_DIFFUSE : name == "roughconductor" ? MTSGPU_BSDF_ROUGHCONDUCTOR
                : name == "roughdielectric" ? MTSGPU_BSDF_ROUGHDIELECTRIC : name == "roughplastic" ? MTSGPU_BSDF_ROUGHPLASTIC
                : name == "conductor" ? MTSGPU_BSDF_CONDUCTOR : name == "dielectric" ? MTSGPU_BSDF_DIELECTRIC
-               : name == "plastic" ? MTSGPU_BSDF_PLASTIC : -1;
+               : name == "plastic" ? MTSGPU_BSDF_PLASTIC
+               : name == "difftrans" ? MTSGPU_BSDF_DIFFTRANS : name == "roughdiffuse" ? MTSGPU_BSDF_ROUGHDIFFUSE
+               : name == "phong" ? MTSGPU_BSDF_PHONG : -1;
         if (d.type < 0) Log(EError, "BSDF \"%s\" is not supported", name.c_str());
         d.distribution = distribution(p);
         d.sample_visible = p.getBoolean("sampleVisible", true);
         d.ensure_energy_conservation = p.getBoolean("ensureEnergyConservation", true);
-        const Float alpha = p.getFloat("alpha", 0.1f);
+        const Float alpha = p.getFloat("alpha", d.type == MTSGPU_BSDF_ROUGHDIFFUSE ? 0.2f : 0.1f);
         d.alpha_u = (float) p.getFloat("alphaU", alpha);
         d.alpha_v = (float) p.getFloat("alphaV", alpha);
         toRGB(p.getSpectrum("reflectance", Spectrum(.5f)), d.reflectance);
-        toRGB(p.getSpectrum("specularReflectance", Spectrum(1.0f)), d.specular_reflectance);
+        toRGB(p.getSpectrum("specularReflectance", Spectrum(d.type == MTSGPU_BSDF_PHONG ? 0.2f : 1.0f)),
+              d.specular_reflectance);
         toRGB(p.getSpectrum("specularTransmittance", Spectrum(1.0f)), d.specular_transmittance);
         toRGB(p.getSpectrum("diffuseReflectance", Spectrum(.5f)), d.diffuse_reflectance);
         d.nonlinear = p.getBoolean("nonlinear", false);
+        /* phong.cpp:60-67, difftrans.cpp:52-57, roughdiffuse.cpp:89-98 */
+        d.exponent = (float) p.getFloat("exponent", 30.0f);
+        toRGB(p.getSpectrum("transmittance", Spectrum(.5f)), d.transmittance);
+        d.use_fast_approx = p.getBoolean("useFastApprox", false) ? 1 : 0;
+        if (d.type == MTSGPU_BSDF_ROUGHDIFFUSE && !p.hasProperty("reflectance"))
+            toRGB(p.getSpectrum("diffuseReflectance", Spectrum(.5f)), d.reflectance);
         if (d.type == MTSGPU_BSDF_ROUGHCONDUCTOR || d.type == MTSGPU_BSDF_CONDUCTOR) {
             /* roughconductor.cpp:169-190 / conductor.cpp: 'material' spectra -> RGB by the
                reference's own InterpolatedSpectrum; the library divides by extEta */
@@ -743,9 +752,14 @@ private:
             if (pn == "alpha" && (d.type == MTSGPU_BSDF_ROUGHCONDUCTOR || d.type == MTSGPU_BSDF_ROUGHDIELECTRIC
                                   || d.type == MTSGPU_BSDF_ROUGHPLASTIC))
                 d.alpha_tex = (*tex)[i].second;
-            else if ((pn == "reflectance" && d.type == MTSGPU_BSDF_DIFFUSE) ||
-                     (pn == "diffuseReflectance" && (d.type == MTSGPU_BSDF_ROUGHPLASTIC || d.type == MTSGPU_BSDF_PLASTIC)))
+            else if (pn == "alpha" && d.type == MTSGPU_BSDF_ROUGHDIFFUSE)
+                d.alpha_tex = (*tex)[i].second;
+            else if ((pn == "reflectance" && (d.type == MTSGPU_BSDF_DIFFUSE || d.type == MTSGPU_BSDF_ROUGHDIFFUSE)) ||
+                     (pn == "diffuseReflectance" && (d.type == MTSGPU_BSDF_ROUGHPLASTIC || d.type == MTSGPU_BSDF_PLASTIC ||
+                                                     d.type == MTSGPU_BSDF_ROUGHDIFFUSE || d.type == MTSGPU_BSDF_PHONG)))
                 d.reflectance_tex = (*tex)[i].second;
+            else if ((pn == "transmittance" || pn == "diffuseTransmittance") && d.type == MTSGPU_BSDF_DIFFTRANS)
+                d.transmittance_tex = (*tex)[i].second;
             else
                 Log(EError, "%s: unsupported texture parameter \"%s\"", name.c_str(), pn.c_str());
         }

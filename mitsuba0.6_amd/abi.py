@@ -14,6 +14,7 @@ STATUS_NAMES = {OK: 'OK', EINVAL: 'EINVAL', EHIP: 'EHIP', ENOMEM: 'ENOMEM', ESTA
 BSDF_DIFFUSE, BSDF_ROUGHCONDUCTOR, BSDF_ROUGHDIELECTRIC, BSDF_ROUGHPLASTIC = 0, 1, 2, 3
 BSDF_CONDUCTOR, BSDF_DIELECTRIC, BSDF_PLASTIC, BSDF_TWOSIDED = 4, 5, 6, 7
 BSDF_MIXTURE, BSDF_BLEND, BSDF_MASK = 8, 9, 10
+BSDF_DIFFTRANS, BSDF_ROUGHDIFFUSE, BSDF_PHONG = 12, 13, 14   # (11: kept free for thindielectric)
 MIXTURE_MAX = 8
 TEX_NONE, TEX_CHECKERBOARD = 0, 1
 ABI_VERSION = 8
@@ -60,7 +61,10 @@ class BsdfDesc(C.Structure):
                 ('num_children', C.c_int32), ('num_weights', C.c_int32),
                 ('children', C.c_int32 * MIXTURE_MAX), ('weights', C.c_float * MIXTURE_MAX),
                 ('weight', C.c_float), ('weight_tex', TextureDesc),
-                ('opacity', _f3), ('opacity_tex', TextureDesc)]
+                ('opacity', _f3), ('opacity_tex', TextureDesc),
+                # appended for difftrans / roughdiffuse / phong
+                ('exponent', C.c_float), ('transmittance', _f3), ('transmittance_tex', TextureDesc),
+                ('use_fast_approx', C.c_int32)]
 
 
 class EmitterDesc(C.Structure):

@@ -882,7 +882,8 @@ int mtsgpu_albedo_factors_host(const mtsgpu_scene_desc *scene, float *factors, c
     }
     for (uint32_t i = 0; i < scene->num_bsdfs; ++i) {
         const MtsgBsdf &b = H.bsdfs[i];
-        factors[i] = b.type == MTSGPU_BSDF_DIFFUSE ? 1.0f
+        // (phong: diffuseReflectance, roughdiffuse: reflectance, as they are; difftrans: 0)
+        factors[i] = (b.type == MTSGPU_BSDF_DIFFUSE || b.type == MTSGPU_BSDF_PHONG || b.type == MTSGPU_BSDF_ROUGHDIFFUSE) ? 1.0f
                    : b.type == MTSGPU_BSDF_PLASTIC ? 1 - b.fdr_ext
                    : b.type == MTSGPU_BSDF_ROUGHPLASTIC ? (b.alpha_tex.type ? -1.0f : b.ftr_ext) : 0.0f;
     }
@@ -907,6 +908,33 @@ int mtsgpu_combo_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out2
     std::memcpy(out21 + 9, c.cdf, sizeof c.cdf);
     std::memcpy(out21 + 18, c.value, sizeof c.value);
     if (flags) *flags = H.bsdfs[bsdf].flags;
+    return MTSGPU_OK;
+}
+
+int mtsgpu_leaf_host(const mtsgpu_scene_desc *scene, uint32_t bsdf, float *out16, int32_t *flags, char *msg,
+                     size_t cap) {
+    if (!scene || !out16) return MTSGPU_EINVAL;
+    HostScene H;
+    std::string err;
+    int rc = mtsg_configure_scene(scene, H, err);
+    if (!rc && (bsdf >= scene->num_bsdfs || H.bsdfs[bsdf].type < MTSGPU_BSDF_DIFFTRANS)) {
+        err = "mtsgpu_leaf_host: not a difftrans, roughdiffuse or phong";
+        rc = MTSGPU_EINVAL;
+    }
+    if (msg && cap) std::snprintf(msg, cap, "%s", err.c_str());
+    if (rc) return rc;
+    const MtsgBsdf &b = H.bsdfs[bsdf];
+    for (int i = 0; i < 3; ++i) {
+        out16[i] = b.refl_tex.type ? b.refl_tex.c0[i] : b.refl[i];
+        out16[3 + i] = b.refl_tex.type ? b.refl_tex.c1[i] : b.refl[i];
+        out16[6 + i] = b.spec_r[i];
+        out16[9 + i] = b.spec_t[i];
+    }
+    out16[12] = b.spec_weight;
+    out16[13] = b.eta;
+    out16[14] = b.alpha_u;
+    out16[15] = (float)b.nonlinear;
+    if (flags) *flags = b.flags;
     return MTSGPU_OK;
 }
 

@@ -4,6 +4,7 @@
 //   conductor, dielectric, plastic             conductor.cpp:164-212, dielectric.cpp:146-201, plastic.cpp:144-216
 //   roughplastic                               roughplastic.cpp:197-300
 //   twosided                                   twosided.cpp:82-103
+//   difftrans, roughdiffuse, phong             difftrans.cpp:52-74, roughdiffuse.cpp:89-122, phong.cpp:60-107
 //   default BSDFs                              Shape::configure (librender/shape.cpp:48-75)
 #include "scene_build_impl.h"
 
@@ -243,6 +244,48 @@ int configure_smooth(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::string &err) {
     return MTSGPU_OK;
 }
 
+// DiffuseTransmitter, RoughDiffuse and Phong: ctor + configure into the fields
+// MtsgBsdf already has (layout.h names which)
+int configure_leaf2(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::string &err) {
+    int rc;
+    const int ens = d.ensure_energy_conservation;
+    if (d.type == MTSGPU_BSDF_DIFFTRANS || d.type == MTSGPU_BSDF_ROUGHDIFFUSE) {
+        const bool dt = d.type == MTSGPU_BSDF_DIFFTRANS;
+        const mtsgpu_texture_desc &t = dt ? d.transmittance_tex : d.reflectance_tex;
+        const float *c = dt ? d.transmittance : d.reflectance;
+        float mx[3];
+        tex_max(t, c, mx);
+        const float sc = energy_scale(mx, ens);
+        for (int i = 0; i < 3; ++i) b.refl[i] = sc != 1.0f ? c[i] * sc : c[i];
+        if ((rc = set_tex(t, sc, b.refl_tex, err))) return rc;
+        if (dt) {
+            b.flags = MTSG_F_DIFF_TRANS | MTSG_F_FRONT | MTSG_F_BACK;
+            return MTSGPU_OK;
+        }
+        // m_alpha = ConstantFloatTexture(alpha) as given: no clamp (roughdiffuse.cpp:97)
+        b.alpha_u = b.alpha_v = d.alpha_u;
+        if ((rc = set_tex(d.alpha_tex, 1.0f, b.alpha_tex, err))) return rc;
+        b.nonlinear = d.use_fast_approx ? 1 : 0;
+        b.flags = MTSG_F_GLOSSY_REFL | MTSG_F_FRONT;
+        return MTSGPU_OK;
+    }
+    // phong: ensureEnergyConservation(specular, diffuse, .., 1.0f), the pair form (bsdf.cpp:115-146):
+    // one scale from the component-wise maximum of the two maxima's sum, on both
+    float dmx[3], sum[3];
+    tex_max(d.reflectance_tex, d.diffuse_reflectance, dmx);
+    for (int i = 0; i < 3; ++i) sum[i] = d.specular_reflectance[i] + dmx[i];
+    const float sc = energy_scale(sum, ens);
+    for (int i = 0; i < 3; ++i) {
+        b.spec_r[i] = sc != 1.0f ? d.specular_reflectance[i] * sc : d.specular_reflectance[i];
+        b.refl[i] = sc != 1.0f ? d.diffuse_reflectance[i] * sc : d.diffuse_reflectance[i];
+    }
+    if ((rc = set_tex(d.reflectance_tex, sc, b.refl_tex, err))) return rc;
+    b.spec_weight = specular_weight(d, sc, b);   // phong.cpp:97-99
+    b.alpha_u = b.alpha_v = d.exponent;
+    b.flags = MTSG_F_GLOSSY_REFL | MTSG_F_DIFF_REFL | MTSG_F_FRONT;
+    return MTSGPU_OK;
+}
+
 int configure_bsdf(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::vector<float> &rt, std::string &err) {
     std::memset(&b, 0, sizeof b);
     b.type = d.type;
@@ -250,6 +293,7 @@ int configure_bsdf(const mtsgpu_bsdf_desc &d, MtsgBsdf &b, std::vector<float> &r
     if (d.type == MTSGPU_BSDF_TWOSIDED) return MTSGPU_OK;   // resolved by configure_twosided
     if (d.type == MTSGPU_BSDF_MIXTURE || d.type == MTSGPU_BSDF_BLEND || d.type == MTSGPU_BSDF_MASK)
         return MTSGPU_OK;                                   // resolved by configure_combo / configure_mask
+    if (d.type >= MTSGPU_BSDF_DIFFTRANS && d.type <= MTSGPU_BSDF_PHONG) return configure_leaf2(d, b, err);
     if (d.type == MTSGPU_BSDF_CONDUCTOR || d.type == MTSGPU_BSDF_DIELECTRIC || d.type == MTSGPU_BSDF_PLASTIC)
         return configure_smooth(d, b, err);
     if (d.type == MTSGPU_BSDF_DIFFUSE) {
@@ -328,8 +372,9 @@ int configure_twosided(const mtsgpu_bsdf_desc &d, int nb, const std::vector<Mtsg
 
 const char *plugin_name(int type) {
     static const char *names[] = {"diffuse", "roughconductor", "roughdielectric", "roughplastic", "conductor", "dielectric",
-                                  "plastic", "twosided", "mixturebsdf", "blendbsdf", "mask"};
-    return type >= 0 && type <= MTSGPU_BSDF_MASK ? names[type] : "?";
+                                  "plastic", "twosided", "mixturebsdf", "blendbsdf", "mask", "?",
+                                  "difftrans", "roughdiffuse", "phong"};
+    return type >= 0 && type <= MTSGPU_BSDF_PHONG ? names[type] : "?";
 }
 
 int refuse(std::string &err, const char *plugin, const std::string &what) {
@@ -391,12 +436,13 @@ int configure_combo(const mtsgpu_bsdf_desc &d, int nb, const std::vector<MtsgBsd
     for (int i = 0; i < c.n; ++i) {
         if (c.child[i] < 0 || c.child[i] >= nb) return refuse(err, me, "nested BSDF index out of range");
         const MtsgBsdf &cb = bsdfs[c.child[i]];
-        if (cb.type >= MTSGPU_BSDF_TWOSIDED)
+        if (cb.type >= MTSGPU_BSDF_TWOSIDED && cb.type <= MTSGPU_BSDF_MASK)
             return refuse(err, me, std::string("nesting a '") + plugin_name(cb.type) +
                                        "' BSDF is not supported (the chain is [mask] -> [twosided] -> [mixturebsdf | "
                                        "blendbsdf] -> leaf)");
-        if (cb.type == MTSGPU_BSDF_ROUGHDIELECTRIC)
-            return refuse(err, me, "a nested 'roughdielectric' BSDF is not supported");
+        // (difftrans: a child on both sides of the surface is not walked by dcombo.h)
+        if (cb.type == MTSGPU_BSDF_ROUGHDIELECTRIC || cb.type == MTSGPU_BSDF_DIFFTRANS)
+            return refuse(err, me, std::string("a nested '") + plugin_name(cb.type) + "' BSDF is not supported");
         if (cb.flags & (MTSG_F_DELTA_REFL | MTSG_F_DELTA_TRANS)) ++deltas;
         flags |= (uint32_t)cb.flags;
     }
@@ -422,6 +468,8 @@ int configure_mask(const mtsgpu_bsdf_desc &d, int nb, const std::vector<MtsgBsdf
     if (cb.type == MTSGPU_BSDF_TWOSIDED)   // (a mixture's or blend's children were checked where it was configured)
         for (int k = 0; k < 2; ++k) rd |= bsdfs[cb.nested[k]].type == MTSGPU_BSDF_ROUGHDIELECTRIC;
     if (rd) return refuse(err, "mask", "a nested 'roughdielectric' BSDF is not supported");
+    if (cb.type == MTSGPU_BSDF_DIFFTRANS)
+        return refuse(err, "mask", std::string("a nested '") + plugin_name(cb.type) + "' BSDF is not supported");
     MtsgCombo c;
     std::memset(&c, 0, sizeof c);
     c.type = d.type;
@@ -466,6 +514,7 @@ int configure_bsdfs(const mtsgpu_scene_desc &D, HostScene &S, std::string &err) 
     for (uint32_t i = 0; i < nb; ++i) {
         const MtsgBsdf &b = S.bsdfs[i];
         if (b.type >= MTSGPU_BSDF_ROUGHPLASTIC || b.refl_tex.type || b.alpha_tex.type) S.ext = true;
+        if (b.type >= MTSGPU_BSDF_DIFFTRANS) S.leaf2 = true;
     }
     for (uint32_t i = 0; i < D.num_meshes; ++i)   // analytic shapes run the EXT | ANA variant
         if (D.meshes[i].shape_type != MTSGPU_SHAPE_TRIMESH) S.ext = true;

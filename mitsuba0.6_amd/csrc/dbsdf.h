@@ -31,7 +31,7 @@ enum { DISTR_BECKMANN = 0, DISTR_GGX = 1, DISTR_PHONG = 2 };
 #endif
 enum { BSDF_DIFFUSE = 0, BSDF_ROUGHCONDUCTOR = 1, BSDF_ROUGHDIELECTRIC = 2, BSDF_ROUGHPLASTIC = 3,
        BSDF_CONDUCTOR = 4, BSDF_DIELECTRIC = 5, BSDF_PLASTIC = 6, BSDF_TWOSIDED = 7,
-       BSDF_MIXTURE = 8, BSDF_BLEND = 9, BSDF_MASK = 10 };   // = MTSGPU_BSDF_* (8-10: dcombo.h)
+       BSDF_MIXTURE = 8, BSDF_BLEND = 9, BSDF_MASK = 10 };   // = MTSGPU_BSDF_* (8-10: dcombo.h; 12-14: dleaf2.h)
 
 __device__ __forceinline__ float tan_theta(f3 v) {           // frame.h:117-122
     float temp = 1 - v.z * v.z;
@@ -121,13 +121,15 @@ struct Distr { int type; float alphaU, alphaV; int sampleVisible; float expU, ex
 // compiles only the lobes and the distribution the scene has, and inlines the
 // microfacet helpers that the generic set calls out of line
 // (profiles/r03_ab_spec_C*.log).
-#define BSET_BITS (MTSG_FEAT_EXT | MTSG_FEAT_DIFF | MTSG_FEAT_GGX | MTSG_FEAT_NORC | MTSG_FEAT_NORD | MTSG_FEAT_INL)
+// LEAF2 (the MTSG_FEAT_SET_LEAF2 kernels): difftrans, roughdiffuse, phong (dleaf2.h).
+#define BSET_BITS (MTSG_FEAT_EXT | MTSG_FEAT_DIFF | MTSG_FEAT_GGX | MTSG_FEAT_NORC | MTSG_FEAT_NORD | MTSG_FEAT_INL | MTSG_FEAT_LEAF2)
 template <int BS> struct BSet {
     static constexpr bool EXT = (BS & MTSG_FEAT_EXT) != 0, DIFF = (BS & MTSG_FEAT_DIFF) != 0;
     static constexpr bool GGX = (BS & MTSG_FEAT_GGX) != 0;
     static constexpr bool RC = (BS & MTSG_FEAT_NORC) == 0, RD = (BS & MTSG_FEAT_NORD) == 0;
     // helpers inline in specialised sets (GGX) and in the wavefront engine's per-type kernels (INL)
     static constexpr bool INL = GGX || (BS & MTSG_FEAT_INL) != 0;
+    static constexpr bool LEAF2 = (BS & MTSG_FEAT_LEAF2) != 0;
 };
 // the distribution type as the variant knows it
 template <int BS> __device__ __forceinline__ int dtype(const Distr &d) { return BSet<BS>::GGX ? (int)DISTR_GGX : d.type; }
@@ -741,6 +743,8 @@ __device__ __noinline__ BSample sm_sample(GBsdf &b, f3 wi, float sx, float sy, f
     return r;
 }
 
+#include "dleaf2.h"   // difftrans, roughdiffuse, phong (BSet<BS>::LEAF2)
+
 // ---- BSDF::eval / pdf / sample --------------------------------------------
 // one BSDF type's eval / pdf / sample bodies (inlined into the dispatchers
 // below, and on their own into the wavefront engine's per-type shade kernels)
@@ -799,6 +803,9 @@ __device__ __forceinline__ f3 rd_eval_body(GBsdf &b, f3 wi, f3 wo, float u, floa
 template <int BS>
 __device__ __forceinline__ f3 bsdf_eval_body(GBsdf &b, glb_f32 *rt, f3 wi, f3 wo, float u, float v) {
     if (b.type == BSDF_DIFFUSE) return diff_eval_body<BS>(b, wi, wo, u, v);
+    if constexpr (BSet<BS>::LEAF2) {
+        if (b.type >= BSDF_DIFFTRANS) return leaf2_eval<BS>(b, wi, wo, u, v);
+    }
     if constexpr (BSet<BS>::EXT) {
         if (b.type == BSDF_ROUGHPLASTIC) return rp_eval<BS>(b, rt, wi, wo, u, v, rp_pre<BS>(b, rt, wi, u, v));
         if (b.type >= BSDF_CONDUCTOR) return sm_eval(b, wi, wo, u, v);
@@ -843,6 +850,9 @@ __device__ __forceinline__ float rd_pdf_body(GBsdf &b, f3 wi, f3 wo, float u, fl
 template <int BS>
 __device__ __forceinline__ float bsdf_pdf_body(GBsdf &b, glb_f32 *rt, f3 wi, f3 wo, float u, float v) {
     if (b.type == BSDF_DIFFUSE) return diff_pdf_body(wi, wo);
+    if constexpr (BSet<BS>::LEAF2) {
+        if (b.type >= BSDF_DIFFTRANS) return leaf2_pdf<BS>(b, wi, wo);
+    }
     if constexpr (BSet<BS>::EXT) {
         if (b.type == BSDF_ROUGHPLASTIC) return rp_pdf<BS>(b, rt, wi, wo, u, v, rp_pre<BS>(b, rt, wi, u, v));
         if (b.type >= BSDF_CONDUCTOR) return sm_pdf(b, wi, wo);
@@ -1001,6 +1011,9 @@ template <int BS>
 BSDF_CALL BSample bsdf_sample(GBsdf &b, glb_f32 *rt, f3 wi, float sx, float sy, float u1d, float u, float v,
                               RpPre pre) {
     if (b.type == BSDF_DIFFUSE) return diff_sample_body<BS>(b, wi, sx, sy, u, v);
+    if constexpr (BSet<BS>::LEAF2) {
+        if (b.type >= BSDF_DIFFTRANS) return leaf2_sample<BS>(b, wi, sx, sy, u, v);
+    }
     if constexpr (BSet<BS>::EXT) {
         if (b.type == BSDF_ROUGHPLASTIC) return rp_sample<BS>(b, rt, wi, sx, sy, u, v, pre);
         if (b.type >= BSDF_CONDUCTOR) return sm_sample(b, wi, sx, sy, u, v);

@@ -16,11 +16,18 @@
 #include "launchers.h"
 
 // BSDF::getDiffuseReflectance(its) of the hit shape's BSDF
+// L2 (the MTSG_FEAT_LEAF2 instantiations): phong's diffuseReflectance (phong.cpp:109-111) and
+// roughdiffuse's reflectance (roughdiffuse.cpp:124-126); difftrans has BSDF's default, whose
+// eval(typeMask = EDiffuseReflection) it rejects
+template <bool L2>
 __device__ __forceinline__ f3 field_albedo(const MtsgDeviceScene &S, GBsdf &top, const Hit &h) {
     constexpr int BS = (int)MTSG_FEAT_EXT;
     GBsdf *b = &top;
     if (b->type == BSDF_TWOSIDED)   // twosided.cpp:198-203: its is handed on as it is
         b = &((GBsdf *)S.bsdfs)[top.nested[h.wi.z > 0 ? 0 : 1]];
+    if constexpr (L2) {
+        if (b->type == BSDF_PHONG || b->type == BSDF_ROUGHDIFFUSE) return bsdf_refl<BS>(*b, h.u, h.v);
+    }
     switch (b->type) {
         case BSDF_DIFFUSE:   // diffuse.cpp:106-108
             return bsdf_refl<BS>(*b, h.u, h.v);
@@ -110,7 +117,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void field_kernel(MtsgLau
                     case MTSG_FIELD_GEO_NORMAL: r = its.geoN; break;
                     case MTSG_FIELD_SH_NORMAL: r = its.sh.n; break;
                     case MTSG_FIELD_UV: r = mk(its.u, its.v, 0.0f); break;
-                    case MTSG_FIELD_ALBEDO: r = field_albedo(S, ((GBsdf *)S.bsdfs)[hs.shapes[its.shape].bsdf], its); break;
+                    case MTSG_FIELD_ALBEDO: r = field_albedo<(FEAT & MTSG_FEAT_LEAF2) != 0>(S, ((GBsdf *)S.bsdfs)[hs.shapes[its.shape].bsdf], its); break;
                     case MTSG_FIELD_SHAPE_INDEX: { const float s = (float)its.shape; r = mk(s, s, s); break; }
                     default: {   // MTSG_FIELD_PRIM_INDEX: the triangle within its mesh; KNoTriangleFlag otherwise
                         const float p = analytic ? (float)0xffffffffu : (float)(prim - FA.shape_first[its.shape]);
@@ -139,6 +146,12 @@ typedef void (*FieldKernelFn)(MtsgLaunch, MtsgFieldArgs);
 static FieldKernelFn field_pick(const MtsgLaunch &L) {
     constexpr int EXT = MTSG_FEAT_EXT, ANA = MTSG_FEAT_EXT | MTSG_FEAT_ANA;
     // thinlens / orthographic / telecentric: one instantiation that holds the analytic shapes too
+    if (L.leaf2) {   // a difftrans / roughdiffuse / phong in the scene: field_albedo knows them
+        constexpr int L2 = MTSG_FEAT_LEAF2;
+        if (L.lens) return L.scene_lds ? field_kernel<true, ANA | MTSG_FEAT_LENS | L2> : field_kernel<false, ANA | MTSG_FEAT_LENS | L2>;
+        if (L.ana) return L.scene_lds ? field_kernel<true, ANA | L2> : field_kernel<false, ANA | L2>;
+        return L.scene_lds ? field_kernel<true, EXT | L2> : field_kernel<false, EXT | L2>;
+    }
     if (L.lens) return L.scene_lds ? field_kernel<true, ANA | MTSG_FEAT_LENS> : field_kernel<false, ANA | MTSG_FEAT_LENS>;
     if (L.ana) return L.scene_lds ? field_kernel<true, ANA> : field_kernel<false, ANA>;
     return L.scene_lds ? field_kernel<true, EXT> : field_kernel<false, EXT>;

@@ -107,6 +107,12 @@ struct MtsgBsdf {            // configured BSDF (after ctor + configure)
     // (mixturebsdf, blendbsdf, mask: nested[0] is the record's index into the side table
     //  MtsgLaunch::combos, nested[1] = -1)
     int32_t nested[2];
+    // The leaves of types 12-14 (dleaf2.h) live in the same fields, so the record and the scene
+    // digest keep their layout:
+    //   difftrans       refl / refl_tex = 'transmittance'
+    //   roughdiffuse    refl / refl_tex = 'reflectance', alpha_u / alpha_tex = 'alpha' as given,
+    //                   nonlinear = 'useFastApprox'
+    //   phong           refl / refl_tex = 'diffuseReflectance', spec_r, spec_weight, alpha_u = 'exponent'
 };
 
 // The combinator BSDFs' own data (mixturebsdf.cpp, blendbsdf.cpp, mask.cpp), a side table next to
@@ -147,21 +153,27 @@ enum { MTSG_FEAT_ENV = 1, MTSG_FEAT_EXT = 2, MTSG_FEAT_ANA = 4,
        // the scene holds a mixturebsdf, blendbsdf or mask (dcombo.h).  Such scenes run one feature set
        // of their own again, the lens set | COMBO: the sensor type (`perspective` too), the delta
        // emitters and the environment are run-time questions there
-       MTSG_FEAT_COMBO = 4096 };
+       MTSG_FEAT_COMBO = 4096,
+       // the scene holds a difftrans, roughdiffuse or phong (dleaf2.h).  One feature
+       // set of its own once more, the combinator set | LEAF2: phong and roughdiffuse may be the
+       // combinators' children, and every other kernel keeps its code
+       MTSG_FEAT_LEAF2 = 8192 };
 #define MTSG_FEAT_SET_DELTA (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA | MTSG_FEAT_DELTA)   // = 1031
 #define MTSG_FEAT_SET_LENS (MTSG_FEAT_SET_DELTA | MTSG_FEAT_LENS)                               // = 3079
 #define MTSG_FEAT_SET_COMBO (MTSG_FEAT_SET_LENS | MTSG_FEAT_COMBO)                              // = 7175
+#define MTSG_FEAT_SET_LEAF2 (MTSG_FEAT_SET_COMBO | MTSG_FEAT_LEAF2)                             // = 15367
 // The scene feature sets the megakernel (path_f<N>.o), direct_kernel and the wavefront shade
 // kernels (wf_shade_f<N>.o) are compiled for, as the numbers the object and function names
 // carry: the one list the declarations, the launch-record check and the picks come from.
 // A pick takes a set by its exact value; any other combination of ENV | EXT | ANA runs set 7,
 // which holds them all, as its `default:` (MTSG_FEAT_SETS_BUT_7 generates the cases).
 // The Makefile's WF_FEATS names the same sets for the build.
-#define MTSG_FEAT_SETS_BUT_7(X) X(0) X(1) X(2) X(3) X(6) X(1031) X(3079) X(7175)
-#define MTSG_FEAT_SETS(X) X(0) X(1) X(2) X(3) X(6) X(7) X(1031) X(3079) X(7175)
+#define MTSG_FEAT_SETS_BUT_7(X) X(0) X(1) X(2) X(3) X(6) X(1031) X(3079) X(7175) X(15367)
+#define MTSG_FEAT_SETS(X) X(0) X(1) X(2) X(3) X(6) X(7) X(1031) X(3079) X(7175) X(15367)
 static_assert(7 == (MTSG_FEAT_ENV | MTSG_FEAT_EXT | MTSG_FEAT_ANA), "set 7 holds ENV, EXT and ANA");
-static_assert(1031 == MTSG_FEAT_SET_DELTA && 3079 == MTSG_FEAT_SET_LENS && 7175 == MTSG_FEAT_SET_COMBO,
-              "MTSG_FEAT_SETS names the delta, lens and combo sets by value");
+static_assert(1031 == MTSG_FEAT_SET_DELTA && 3079 == MTSG_FEAT_SET_LENS && 7175 == MTSG_FEAT_SET_COMBO &&
+                  15367 == MTSG_FEAT_SET_LEAF2,
+              "MTSG_FEAT_SETS names the delta, lens, combo and leaf2 sets by value");
 // whether n is one of MTSG_FEAT_SETS (path_f.hip, wf_shade_f.hip: their -D value)
 constexpr bool mtsg_is_feat_set(int n) {
 #define MTSG_FEAT_IS(N) n == N ||
@@ -440,6 +452,8 @@ struct MtsgLaunch {
     uint32_t combo;                        // kernel variant: a mixturebsdf / blendbsdf / mask in the scene (the
                                            // MTSG_FEAT_SET_COMBO kernels; host side only, like `delta`)
     const MtsgCombo *combos;               // the combinators' side table (those kernels only), or null
+    uint32_t leaf2;                        // kernel variant: a difftrans / roughdiffuse / phong in the scene (the
+                                           // MTSG_FEAT_SET_LEAF2 kernels; host side only, like `delta`)
 };
 
 // The field pass (field_kernel.hip; FieldIntegrator::Li, integrators/misc/field.cpp:124-177):

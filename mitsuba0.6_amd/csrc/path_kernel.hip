@@ -228,6 +228,8 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                    ANA = (FEAT & MTSG_FEAT_ANA) != 0, DELTA = (FEAT & MTSG_FEAT_DELTA) != 0,
                    LENS = (FEAT & MTSG_FEAT_LENS) != 0,   // the sensor's own ray (dsensor.h)
                    COMBO = (FEAT & MTSG_FEAT_COMBO) != 0; // mixturebsdf / blendbsdf / mask (dcombo.h)
+    // the chain's leaf functions: the EXT set, with types 12-14 in the MTSG_FEAT_SET_LEAF2 kernel (dleaf2.h)
+    constexpr int CBS = (int)MTSG_FEAT_EXT | (FEAT & (int)MTSG_FEAT_LEAF2);
     extern __shared__ __attribute__((aligned(64))) uint32_t lds[];   // (dsampler.h sobol_row)
     const MtsgDeviceScene &S = L.scene;
     // the delta-emitter feature set is compiled with ENV; its scenes need not have an environment
@@ -322,7 +324,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                             bool combo = false;
                             if constexpr (COMBO) {
                                 if (direct_is_combo(bsdf)) {
-                                    const EvalPdf ep = combo_eval_pdf<MTSG_FEAT_EXT>((GBsdf *)S.bsdfs, (GCombo *)L.combos,
+                                    const EvalPdf ep = combo_eval_pdf<CBS>((GBsdf *)S.bsdfs, (GCombo *)L.combos,
                                                                                      (glb_f32 *)S.rtrans, &bsdf, its.wi, wo,
                                                                                      its.u, its.v);
                                     bsdfVal = ep.val;
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(BLOCK, MTSG_WAVES_PER_EU) void direct_kernel(MtsgLa
                     BSample bs;
                     if (COMBO && direct_is_combo(bsdf)) {
                         if constexpr (COMBO)
-                            bs = combo_sample<MTSG_FEAT_EXT>((GBsdf *)S.bsdfs, (GCombo *)L.combos, (glb_f32 *)S.rtrans, &bsdf,
+                            bs = combo_sample<CBS>((GBsdf *)S.bsdfs, (GCombo *)L.combos, (glb_f32 *)S.rtrans, &bsdf,
                                                              its.wi, bx, by, its.u, its.v);
                     } else {
                         bs = bsdf_sample_2s<EXT>(S, bsdf, its, bx, by, u1d);
@@ -727,9 +729,10 @@ size_t mtsg_path_lds_bytes(const MtsgLaunch &L) {
 }
 
 // (the MTSG_FEAT_LENS kernels are built without the queue: dmega.h QUEUE)
-bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L) && !L.lens && !L.combo; }
+bool mtsg_path_start_queue(const MtsgLaunch &L) { return mtsg_start_queue(L) && !L.lens && !L.combo && !L.leaf2; }
 
 int mtsg_path_features(const MtsgLaunch &L) {
+    if (L.leaf2) return MTSG_FEAT_SET_LEAF2;   // difftrans / roughdiffuse / phong: the combinator set | LEAF2
     if (L.combo) return MTSG_FEAT_SET_COMBO;   // mixturebsdf / blendbsdf / mask: the one set that holds everything
     if (L.lens) return MTSG_FEAT_SET_LENS;     // thinlens / orthographic / telecentric: the one set that holds everything
     if (L.delta) return MTSG_FEAT_SET_DELTA;   // delta-emitter scenes: the one set that holds everything
@@ -742,7 +745,7 @@ int mtsg_path_features(const MtsgLaunch &L) {
 // (render_plan.cpp plan_render, L.bset).  Every feature set has all 7 sets compiled (path_f.hip);
 // small scenes staged in LDS and the direct integrator take the generic kernel.
 static int spec_bits(const MtsgLaunch &L) {
-    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta || L.lens || L.combo) return 0;   // (delta, lens, combo: the generic set only)
+    if (L.scene_lds || L.integrator == MTSG_INTEGRATOR_DIRECT || L.delta || L.lens || L.combo || L.leaf2) return 0;   // (delta, lens, combo, leaf2: the generic set only)
     const int b = ((L.bset & MTSG_FEAT_GGX) ? 1 : 0) | ((L.bset & MTSG_FEAT_NORD) ? 2 : 0) | ((L.bset & MTSG_FEAT_NORC) ? 4 : 0);
     return b | ((b && (L.bset & MTSG_FEAT_NOREFN) && (mtsg_path_features(L) & MTSG_FEAT_ENV)) ? 8 : 0);
 }

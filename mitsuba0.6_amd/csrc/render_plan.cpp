@@ -199,7 +199,7 @@ uint32_t plan_bset(const HostScene &H, const mtsgpu_render_params &P, const Rend
     for (int a = 0; a < 3; ++a) extent = std::max(extent, std::max(std::fabs(H.aabb_min[a]), std::fabs(H.aabb_max[a])));
     // (the set kernels are built without strictNormals: MTSG_FEAT_NOSTRICT)
     const bool lens = H.cam_lens.type != MTSG_SENSOR_PERSPECTIVE;   // (the lens set, like the delta set: the generic kernel)
-    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals || !H.deltas.empty() || lens || !H.combos.empty()) ? 0u
+    uint32_t bset = (K.no_bsdf_sets || !(extent < 32768.0f) || P.strict_normals || !H.deltas.empty() || lens || !H.combos.empty() || H.leaf2) ? 0u
                     : (ggx ? (uint32_t)MTSG_FEAT_GGX : 0u) | (rc ? 0u : (uint32_t)MTSG_FEAT_NORC) |
                           (rd ? 0u : (uint32_t)MTSG_FEAT_NORD);
     // envmap-only scenes (no area light, no constant emitter): the set kernels without
@@ -230,7 +230,9 @@ void plan_variant(MtsgLaunch &L, const HostScene &H, const mtsgpu_render_params 
     // mixturebsdf / blendbsdf / mask: the MTSG_FEAT_SET_COMBO kernels, which hold the lens set's code
     // and ask the sensor type at run time; like that set the generic BSDF set, no start queue, no early miss
     L.combo = H.combos.empty() ? 0u : 1u;
-    L.all_diffuse = (K.no_diff_variant || L.delta || L.lens || L.combo) ? 0u : 1u;
+    // difftrans / roughdiffuse / phong: the MTSG_FEAT_SET_LEAF2 kernels, the combinator set | LEAF2, on the same terms
+    L.leaf2 = H.leaf2 ? 1u : 0u;
+    L.all_diffuse = (K.no_diff_variant || L.delta || L.lens || L.combo || L.leaf2) ? 0u : 1u;
     for (const MtsgBsdf &b : H.bsdfs) L.all_diffuse &= b.type == MTSGPU_BSDF_DIFFUSE ? 1u : 0u;
     L.bset = plan_bset(H, P, K);
     // large scenes are latency-bound: run 4 waves/SIMD when 4 blocks' traversal
@@ -530,14 +532,16 @@ WfPlan plan_wavefront(const RenderPlan &plan, const HostScene &H, const RenderKn
 // such emitters in the scene), the field pass's included;
 // 1 << 20 (MTSGPU_VARIANT_COMBO): the MTSG_FEAT_SET_COMBO instantiations of scenes with a mixturebsdf,
 // blendbsdf or mask (they hold the lens and delta code too: bits 19 and 18 say what the scene has)
+// 1 << 21 (MTSGPU_VARIANT_LEAF2): the MTSG_FEAT_SET_LEAF2 instantiations of scenes with a difftrans,
+// roughdiffuse or phong (they hold the combinators' code too: bit 20 says whether the scene has one)
 // (tests and A/B logs read it)
 uint64_t plan_variant_word(const RenderPlan &plan) {
     const MtsgLaunch &L = plan.L;
     const uint64_t lbit = L.lens ? 1ull << 19 : 0;
-    const uint64_t dbit = (L.delta ? 1ull << 18 : 0) | lbit | (L.combo ? 1ull << 20 : 0);
+    const uint64_t dbit = (L.delta ? 1ull << 18 : 0) | lbit | (L.combo ? 1ull << 20 : 0) | (L.leaf2 ? 1ull << 21 : 0);
     if (plan.engine == MTSG_ENGINE_WAVEFRONT) return (1ull << 16) | dbit;
     if (plan.engine == MTSG_ENGINE_FIELDS)   // field_kernel<SCENE_LDS, ..>: 1 << 17 | SCENE_LDS << 12
-        return (1ull << 17) | ((uint64_t)L.scene_lds << 12) | lbit;
+        return (1ull << 17) | ((uint64_t)L.scene_lds << 12) | lbit | (L.leaf2 ? 1ull << 21 : 0);   // (| its LEAF2 instantiation)
     const int v = mtsg_path_variant(L);
     return dbit | (uint64_t)((v & 0xff) | (int)(L.waves << 8) | (int)(L.scene_lds << 12) | (plan.instr ? 1 << 13 : 0) |
                       ((v & MTSG_FEAT_NOSTRICT) ? 1 << 14 : 0) | ((v & MTSG_FEAT_NOREFN) ? 1 << 15 : 0));

@@ -59,6 +59,7 @@ struct HostScene {
     // mixturebsdf / blendbsdf / mask records (MtsgBsdf::nested[0] indexes them; MtsgLaunch::combos).
     // Not empty: the MTSG_FEAT_SET_COMBO kernels.  (Not one of mtsgpu_scene_digest_host's members.)
     std::vector<MtsgCombo> combos;
+    bool leaf2 = false;   // a difftrans, roughdiffuse or phong: the MTSG_FEAT_SET_LEAF2 kernels
     // launch constants of the scene, formed where it is uploaded (render_plan.cpp scene_scan_n, scene_one_emitter)
     struct {
         uint32_t scan_n[6];     // as MtsgLaunch::scan_n: records | plane pairs << 16

@@ -34,7 +34,8 @@ EXPORTS = ['mtsgpu_create', 'mtsgpu_upload_scene', 'mtsgpu_film_border', 'mtsgpu
            'mtsgpu_bvh_host', 'mtsgpu_group_member_params', 'mtsgpu_render_pixels',
            'mtsgpu_xml_bsdf', 'mtsgpu_xml_bsdf_ex', 'mtsgpu_scan_host', 'mtsgpu_index_host', 'mtsgpu_lookup_host',
            'mtsgpu_face_normals_host', 'mtsgpu_render_fields', 'mtsgpu_render_fields_device', 'mtsgpu_develop_multi',
-           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_combo_host', 'mtsgpu_develop_ldr',
+           'mtsgpu_develop_multi_device', 'mtsgpu_albedo_factors_host', 'mtsgpu_combo_host', 'mtsgpu_leaf_host',
+           'mtsgpu_develop_ldr',
            'mtsgpu_develop_ldr_device', 'mtsgpu_plan_host']
 
 _lib = None
@@ -176,6 +177,27 @@ def combo_host(scene, index):
             'flags': flags.value}
 
 
+def leaf_host(scene, index):
+    """What configure() derives for the difftrans / roughdiffuse / phong at `index` of
+    scene.flat_bsdfs(), on the host without a device (mtsgpu_leaf_host): {'reflectance' (after
+    ensureEnergyConservation; roughdiffuse reflectance, phong diffuseReflectance, difftrans
+    transmittance; a checkerboard's color0), 'reflectance1' (its color1, or the same),
+    'specularReflectance' and 'specularSamplingWeight' (phong), 'alpha' (roughdiffuse's alpha or
+    phong's exponent), 'useFastApprox', 'flags'}."""
+    L = load_library()
+    L.mtsgpu_leaf_host.argtypes = [C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                   C.c_char_p, C.c_size_t]
+    d = scene.desc()
+    out = np.zeros(16, np.float32)
+    flags = C.c_int32(0)
+    buf = C.create_string_buffer(512)
+    rc = L.mtsgpu_leaf_host(C.byref(d), index, abi.fptr(out), C.byref(flags), buf, 512)
+    if rc != 0:
+        raise MtsgpuError(rc, buf.value.decode())
+    return {'reflectance': out[0:3].copy(), 'reflectance1': out[3:6].copy(), 'specularReflectance': out[6:9].copy(),
+            'specularSamplingWeight': out[12], 'alpha': out[14], 'useFastApprox': bool(out[15]), 'flags': flags.value}
+
+
 KD_KEYS = ('nodes', 'indices', 'inner', 'leaves', 'nonempty_leaves', 'retracted', 'pruned', 'max_depth')
 
 
@@ -274,6 +296,9 @@ VARIANT_LENS = 1 << 19
 # ... and the instantiations of scenes with a mixturebsdf, blendbsdf or mask (MTSG_FEAT_SET_COMBO = 7175; they hold the
 # lens and delta code too, bits 18 and 19 then say what the scene has)
 VARIANT_COMBO = 1 << 20
+# ... and the instantiations of scenes with a difftrans, roughdiffuse or phong (MTSG_FEAT_SET_LEAF2 =
+# 15367; they hold the combinators' code too, bit 20 then says whether the scene has one)
+VARIANT_LEAF2 = 1 << 21
 
 
 def kernel_variant_of(word):
@@ -284,12 +309,13 @@ def kernel_variant_of(word):
     if c & (3 << 16):   # the wavefront engine, or a field pass (field_kernel)
         return None
     feat = ((c & 0xff) | (256 if c & (1 << 14) else 0) | (512 if c & (1 << 15) else 0) |
-            (1024 if c & (VARIANT_DELTA | VARIANT_LENS | VARIANT_COMBO) else 0) |
-            (2048 if c & (VARIANT_LENS | VARIANT_COMBO) else 0) | (4096 if c & VARIANT_COMBO else 0))
+            (1024 if c & (VARIANT_DELTA | VARIANT_LENS | VARIANT_COMBO | VARIANT_LEAF2) else 0) |
+            (2048 if c & (VARIANT_LENS | VARIANT_COMBO | VARIANT_LEAF2) else 0) |
+            (4096 if c & (VARIANT_COMBO | VARIANT_LEAF2) else 0) | (8192 if c & VARIANT_LEAF2 else 0))
     instr, lds, waves = bool(c & (1 << 13)), bool(c & (1 << 12)), (c >> 8) & 0xf
     b = lambda v: 'true' if v else 'false'
     return {'instr': instr, 'scene_lds': lds, 'feat': feat, 'waves': waves, 'delta': bool(c & VARIANT_DELTA),
-            'lens': bool(c & VARIANT_LENS), 'combo': bool(c & VARIANT_COMBO),
+            'lens': bool(c & VARIANT_LENS), 'combo': bool(c & VARIANT_COMBO), 'leaf2': bool(c & VARIANT_LEAF2),
             'name': 'path_kernel<%s, %s, %d, %d>' % (b(instr), b(lds), feat, waves)}
 
 

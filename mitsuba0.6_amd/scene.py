@@ -67,7 +67,9 @@ BSDF_TYPES = {'diffuse': abi.BSDF_DIFFUSE, 'roughconductor': abi.BSDF_ROUGHCONDU
               'roughdielectric': abi.BSDF_ROUGHDIELECTRIC, 'roughplastic': abi.BSDF_ROUGHPLASTIC,
               'conductor': abi.BSDF_CONDUCTOR, 'dielectric': abi.BSDF_DIELECTRIC,
               'plastic': abi.BSDF_PLASTIC, 'twosided': abi.BSDF_TWOSIDED,
-              'mixturebsdf': abi.BSDF_MIXTURE, 'blendbsdf': abi.BSDF_BLEND, 'mask': abi.BSDF_MASK}
+              'mixturebsdf': abi.BSDF_MIXTURE, 'blendbsdf': abi.BSDF_BLEND, 'mask': abi.BSDF_MASK,
+              'difftrans': abi.BSDF_DIFFTRANS, 'roughdiffuse': abi.BSDF_ROUGHDIFFUSE, 'phong': abi.BSDF_PHONG}
+
 # the BSDFs that hold other BSDFs in `nested`
 WRAPPERS = ('twosided', 'mixturebsdf', 'blendbsdf', 'mask')
 
@@ -84,7 +86,13 @@ class BSDF:
     BSDF, up to 8), `blendbsdf` (weight: a float or a Checkerboard; two nested) and `mask`
     (opacity: a spectrum or a Checkerboard; one nested).  One chain is supported,
     [mask] -> [twosided] -> [mixturebsdf | blendbsdf] -> leaf; the library refuses the
-    rest when the scene is checked or uploaded."""
+    rest when the scene is checked or uploaded.
+
+    Three more leaves: `difftrans` (transmittance: a spectrum or a Checkerboard, default
+    0.5), `roughdiffuse` (reflectance and alpha, default 0.2, each possibly a Checkerboard;
+    useFastApprox) and `phong` (exponent, default 30; diffuseReflectance, possibly a
+    Checkerboard, default 0.5; specularReflectance, default 0.2).  phong and roughdiffuse may
+    be nested in twosided and the combinators; difftrans may not."""
     type: str = 'diffuse'
     reflectance: object = (0.5, 0.5, 0.5)
     distribution: str = 'beckmann'
@@ -92,7 +100,7 @@ class BSDF:
     alphaU: Optional[float] = None
     alphaV: Optional[float] = None
     sampleVisible: bool = True
-    specularReflectance: tuple = (1.0, 1.0, 1.0)
+    specularReflectance: Optional[tuple] = None   # None: the plugin's default, Spectrum(1); phong's is 0.2 (phong.cpp:63)
     specularTransmittance: tuple = (1.0, 1.0, 1.0)
     eta: Optional[tuple] = None        # roughconductor: explicit RGB eta/k override `material`
     k: Optional[tuple] = None
@@ -108,6 +116,13 @@ class BSDF:
     weights: Optional[list] = None     # mixturebsdf 'weights'
     weight: object = 0.5               # blendbsdf 'weight' (blendbsdf.cpp:63)
     opacity: object = 0.5              # mask 'opacity' (mask.cpp:76-77)
+    exponent: float = 30.0             # phong 'exponent' (phong.cpp:65)
+    transmittance: object = (0.5, 0.5, 0.5)   # difftrans 'transmittance' (difftrans.cpp:54-56)
+    useFastApprox: bool = False        # roughdiffuse 'useFastApprox' (roughdiffuse.cpp:96)
+
+    def __post_init__(self):
+        if self.specularReflectance is None:
+            self.specularReflectance = (0.2, 0.2, 0.2) if self.type == 'phong' else (1.0, 1.0, 1.0)
 
     def int_ior(self):
         if self.intIOR is not None:
@@ -153,10 +168,22 @@ class BSDF:
                 raise ValueError("Microfacet model: both 'alphaU' and 'alphaV' must be specified.")
             au, av = float(self.alphaU), float(self.alphaV)
         else:
-            au = av = 0.1
+            au = av = 0.2 if self.type == 'roughdiffuse' else 0.1   # (roughdiffuse.cpp:97)
         d.alpha_u, d.alpha_v = au, av
+        if self.type == 'phong':
+            if isinstance(self.exponent, Checkerboard):
+                raise NotImplementedError("phong: a textured 'exponent' is not on the GPU path")
+            d.exponent = float(self.exponent)
+        if self.type == 'phong' and isinstance(self.specularReflectance, Checkerboard):
+            raise NotImplementedError("phong: a textured 'specularReflectance' is not on the GPU path")
+        if self.type == 'difftrans':
+            if isinstance(self.transmittance, Checkerboard):
+                self.transmittance.fill(d.transmittance_tex)
+            else:
+                d.transmittance[:] = _spec(self.transmittance)
+        d.use_fast_approx = int(self.useFastApprox)
         if isinstance(self.reflectance, Checkerboard):
-            if self.type == 'diffuse':
+            if self.type in ('diffuse', 'roughdiffuse'):
                 self.reflectance.fill(d.reflectance_tex)
         else:
             d.reflectance[:] = _spec(self.reflectance)
@@ -168,7 +195,7 @@ class BSDF:
             eta, k = conductor_rgb(self.material or 'Cu')
             d.eta[:] = self.eta if self.eta is not None else eta
             d.k[:] = self.k if self.k is not None else k
-        if self.type in ('roughplastic', 'plastic'):
+        if self.type in ('roughplastic', 'plastic', 'phong'):
             if isinstance(self.diffuseReflectance, Checkerboard):
                 self.diffuseReflectance.fill(d.reflectance_tex)
             else:

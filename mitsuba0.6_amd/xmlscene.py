@@ -326,6 +326,28 @@ class XMLSceneLoader:
                         diffuseReflectance=tex.get('diffuseReflectance', p.get('diffuseReflectance', (0.5, 0.5, 0.5))),
                         nonlinear=p.get('nonlinear', False),
                         ensureEnergyConservation=p.get('ensureEnergyConservation', True))
+        if t in ('difftrans', 'roughdiffuse', 'phong'):
+            # difftrans.cpp:52-57, roughdiffuse.cpp:89-98, phong.cpp:60-67; addChild of each
+            allowed = {'difftrans': ('transmittance', 'diffuseTransmittance'),
+                       'roughdiffuse': ('reflectance', 'diffuseReflectance', 'alpha'), 'phong': ('diffuseReflectance',)}[t]
+            known = ('exponent', 'specularReflectance') if t == 'phong' else ()
+            for name, ch in p.children:
+                if ch.tag == 'texture' and name in known:
+                    raise NotImplementedError('%s: a textured "%s" is not on the GPU path' % (t, name))
+            tex = self._tex_params(p, allowed)
+            ens = p.get('ensureEnergyConservation', True)
+            if t == 'difftrans':
+                tr = tex.get('transmittance', tex.get('diffuseTransmittance', p.get('transmittance', (0.5, 0.5, 0.5))))
+                return BSDF(t, transmittance=tr, ensureEnergyConservation=ens)
+            if t == 'roughdiffuse':
+                # 'reflectance', else 'diffuseReflectance' (roughdiffuse.cpp:91-94)
+                refl = p.get('reflectance', p.get('diffuseReflectance', (0.5, 0.5, 0.5)))
+                refl = tex.get('reflectance', tex.get('diffuseReflectance', refl))
+                return BSDF(t, reflectance=refl, alpha=tex.get('alpha', float(p.get('alpha', 0.2))),
+                            useFastApprox=bool(p.get('useFastApprox', False)), ensureEnergyConservation=ens)
+            return BSDF(t, diffuseReflectance=tex.get('diffuseReflectance', p.get('diffuseReflectance', (0.5, 0.5, 0.5))),
+                        specularReflectance=p.get('specularReflectance', (0.2, 0.2, 0.2)),
+                        exponent=float(p.get('exponent', 30.0)), ensureEnergyConservation=ens)
         if t == 'twosided':                        # twosided.cpp:63-103, 193-205 (addChild)
             nested = [self.make_bsdf(c) for _, c in p.children if c.tag == 'bsdf']
             for _, c in p.children:
@@ -338,6 +360,8 @@ class XMLSceneLoader:
             for nb in nested:
                 if nb.type in ('twosided', 'mask'):
                     raise NotImplementedError('twosided: a nested "%s" BSDF is not on the GPU path' % nb.type)
+                if nb.type == 'difftrans':   # TwoSidedBRDF::configure (twosided.cpp:96-98)
+                    raise SceneError('Only materials without a transmission component can be nested!')
             return BSDF('twosided', nested=nested)
         if t in ('mixturebsdf', 'blendbsdf', 'mask'):
             # mixturebsdf.cpp:67-98, 279-287; blendbsdf.cpp:60-75, 272-284; mask.cpp:74-78, 225-237 (addChild).
@@ -357,6 +381,9 @@ class XMLSceneLoader:
                 below += nb.nested + [x for y in nb.nested for x in y.nested]
             if any(x.type == 'roughdielectric' for x in below):
                 raise NotImplementedError('%s: a nested "roughdielectric" BSDF is not on the GPU path' % t)
+            for x in below:
+                if x.type == 'difftrans':
+                    raise NotImplementedError('%s: a nested "%s" BSDF is not on the GPU path' % (t, x.type))
             ens = p.get('ensureEnergyConservation', True)
             if t == 'mixturebsdf':
                 toks = [x for x in re.split(r'[ ,;]+', str(p.get('weights', ''))) if x]
@@ -386,7 +413,8 @@ class XMLSceneLoader:
                         ensureEnergyConservation=ens)
         raise NotImplementedError('BSDF plugin "%s" is not on the GPU path (diffuse, roughconductor, '
                                   'roughdielectric, roughplastic, conductor, dielectric, plastic, '
-                                  'twosided, mixturebsdf, blendbsdf, mask)' % t)
+                                  'twosided, mixturebsdf, blendbsdf, mask, difftrans, '
+                                  'roughdiffuse, phong)' % t)
 
     def make_area(self, p):
         if p.plugin != 'area':
@@ -781,6 +809,19 @@ def _bsdf_xml(b, ind, bid=None):
             L += _bsdf_xml(nb, i2)
     elif b.type == 'diffuse':
         L.append(i2 + _spec_xml('reflectance', b.reflectance))
+    elif b.type in ('difftrans', 'roughdiffuse', 'phong'):
+        if b.type == 'difftrans':
+            L.append(i2 + _spec_xml('transmittance', b.transmittance))
+        elif b.type == 'roughdiffuse':
+            L.append(i2 + _spec_xml('reflectance', b.reflectance))
+            L.append(i2 + (_checker_xml('alpha', b.alpha) if isinstance(b.alpha, Checkerboard)
+                           else '<float name="alpha" value="%s"/>' % _fmt(0.2 if b.alpha is None else b.alpha)))
+            L.append(i2 + '<boolean name="useFastApprox" value="%s"/>' % str(bool(b.useFastApprox)).lower())
+        else:
+            L.append(i2 + _spec_xml('diffuseReflectance', b.diffuseReflectance))
+            L.append(i2 + _rgb('specularReflectance', b.specularReflectance))
+            L.append(i2 + '<float name="exponent" value="%s"/>' % _fmt(b.exponent))
+        L.append(i2 + '<boolean name="ensureEnergyConservation" value="%s"/>' % str(bool(b.ensureEnergyConservation)).lower())
     else:
         if b.type.startswith('rough'):
             L.append(i2 + '<string name="distribution" value="%s"/>' % b.distribution)
